@@ -12,7 +12,11 @@ over one 64-graph batch per rank; batches are pre-assembled and resident in HBM 
 Data-parallel: one process per GPU, each rank trains its own 64-graph batch (weak scaling; the
 attention couples all graphs of a batch, so a batch never splits across GPUs).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the
+  line can carry (CPU baseline, the other precision policies, the on-the-fly pipeline, the other BASELINE configs,
+  the neighbour-attention line, the live roofline probes and the gather roofline); the switches below
+  (--cpu-baseline, --fp32-steps, --pipeline-steps, --configs, --neighbors-line, --no-roofline) select among them.
   N > 1: run under `torch.distributed.run --nproc-per-node N` (the driver's form), or let bench.py
   start that launcher itself when WORLD_SIZE is unset (the parent never touches the GPU).
 """
@@ -60,7 +64,15 @@ def parse():
                     help="gradient all-reduce per layer under the backward (overlap) or after it")
     ap.add_argument("--force-dist", action="store_true",
                     help="init the RCCL process group even at one rank (exercises the DP path on one GPU)")
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline value does not need: CPU baseline, other precision policies, "
+                         "the on-the-fly pipeline, the other configs, the neighbour-attention line and the rooflines "
+                         "(each has its own switch below); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left its caller -- loss, flat parameters "
+                         "and flat gradients -- as DIR/<name>.npy (float32; a fixed seeded sample of each array "
+                         "when they exceed 64 MB in all, as for --workload c5)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--num-neighbors", type=int, default=16)
@@ -620,6 +632,8 @@ def run_c5(args):
             dist.barrier()
         elapsed = time.perf_counter() - t0
         loss = float(trainer.loss.item())
+        if args.dump_outputs and rank == 0:   # before the optimizer roofline steps the parameters again
+            dump_outputs(args.dump_outputs, trainer_outputs(trainer))
     finally:
         if runner is not None:
             runner.close()
@@ -629,7 +643,7 @@ def run_c5(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     opt_roof = attn = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         n = trainer.flat.n
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 20
@@ -675,7 +689,7 @@ def run_c5(args):
            "roofline": step_roof, "optimizer": opt_roof, "step_hbm": step_roof, "attention_kernel": attn,
            "cpu_baseline": None,
            "samples": "512 log-uniform ids drawn on the host every step (C++ sampler) and copied to HBM"}
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = unsup_cpu_baseline(host, sids_host, sd0, V, args.num_timesteps, args.lr,
                                                  max(3, args.cpu_steps))
     if dist is not None:
@@ -752,10 +766,12 @@ def run_small(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     loss = float(trainer.loss.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer_outputs(trainer))
     if runner is not None:
         runner.close()
     cpu = None
-    if args.cpu_baseline:
+    if args.full and args.cpu_baseline:
         threads, how = cpu_threads()
         torch.set_num_threads(threads)
         params = {kk: v.detach().cpu().clone().requires_grad_(True) for kk, v in sd0.items()}
@@ -865,6 +881,32 @@ def largest_kernel(workload):
     return {"note": f"no kernel-trace summary of build {bid} for {workload} under profiles/"}
 
 
+DUMP_BUDGET = 64 * 10 ** 6   # bytes of --dump-outputs, all arrays together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor) as path/<name>.npy in float32.  At most DUMP_BUDGET bytes of
+    array data in all: when the arrays exceed it, each is cut to the same fraction of its elements (rounded down, at
+    least one; the budget keeps one element per array aside for that), at sorted positions drawn by a generator
+    seeded with a constant, so two runs with the same arguments keep the same positions."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    frac = 1.0 if total <= DUMP_BUDGET else (DUMP_BUDGET - 4 * len(arrays)) / total
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().reshape(-1).to(torch.float32).cpu().numpy()
+        if frac < 1.0:
+            rng = np.random.default_rng(20240 + i)
+            keep = np.sort(rng.choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def trainer_outputs(trainer):
+    """What a caller of trainer.step() holds after it: the returned loss and the state the step wrote (the flat
+    parameter buffer after clip + Adam, the flat gradient buffer of that step)."""
+    return {"loss": trainer.loss, "params": trainer.flat.flat, "grads": trainer.flat.gflat}
+
+
 _JSON_OUT = None
 
 
@@ -953,7 +995,7 @@ def main():
              "dk": LIB.ROLE_DK}
     role = ROLES[args.probe]
     # (graph replay: the probe's events would belong to the capture, so no live probe)
-    probing = not args.no_roofline and args.attention == "nodes" and native.enabled() and not graph
+    probing = args.full and not args.no_roofline and args.attention == "nodes" and native.enabled() and not graph
     per_step = args.num_hidden_layers * args.num_timesteps
     try:
         if graph:   # one captured HIP graph per distinct batch, captured (not run) before the warmup
@@ -987,6 +1029,8 @@ def main():
         if runner is not None:
             runner.close()
     loss = float(trainer.loss.item())
+    if args.dump_outputs and rank == 0:   # before any further pass steps the trainer again
+        dump_outputs(args.dump_outputs, trainer_outputs(trainer))
     # optional per-GEMM family pass: the same K steps again, serialised, with per-GEMM HIP events
     K.REC.records.clear()
     rec_elapsed = None
@@ -1090,9 +1134,10 @@ def main():
                                          "boundary unit moves its dW1 row; the reference's own fp32 misses its fp64 "
                                          "run by up to 2e-2); outputs and loss within 1e-3 of it",
                       "fp32": "within 4.1e-6 in every case and mode; its C4 rate is the 'fp32' object"}}
-    if rank == 0:
+    if rank == 0 and args.full:   # (--no-roofline is the live probes' switch, not the gather's)
         out["gather"] = gather_roofline(used[0], d, args.ff_hidden_size, K, dev)
-    if rank == 0 and world == 1 and args.fp32_steps > 0 and args.precision != "fp32" and args.attention == "nodes":
+    extras = args.full and rank == 0 and world == 1   # what only --full measures (see parse())
+    if extras and args.fp32_steps > 0 and args.precision != "fp32" and args.attention == "nodes":
         # the other precision policies' price on the same batches: every product exact fp32,
         # the exact-fp32 forward, and the policies of bf16x3 / fwd6 / fwdh that are not the headline
         out["fp32"] = exact_line(args, batches, sd0, dev, d, C, "fp32")
@@ -1101,11 +1146,11 @@ def main():
             for other in ("bf16x3", "fwd6", "fwdh"):
                 if other != args.precision:
                     out[other] = exact_line(args, batches, sd0, dev, d, C, other)
-    if rank == 0 and world == 1 and args.pipeline_steps > 0 and args.attention == "nodes":
+    if extras and args.pipeline_steps > 0 and args.attention == "nodes":
         out["pipeline"] = pipeline_rate(store, trainer, args, dev, value)
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if extras and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(host[args.warmup % nb], sd0, args, d, C)
-    if rank == 0 and world == 1 and args.configs and args.attention == "nodes" and not args.force_dist:
+    if extras and args.configs and args.attention == "nodes" and not args.force_dist:
         # BASELINE configs[4], [1], [2] timed in this run too (driver-timed C5 / C2 / C3): each
         # object is the line its own --workload run prints
         import copy
@@ -1113,13 +1158,13 @@ def main():
         torch.cuda.empty_cache()
         for wl in ("c5", "c2", "c3"):
             a = copy.copy(args)
-            a.workload, a.steps, a.warmup, a.graph = wl, args.config_steps, 5, -1
+            a.workload, a.steps, a.warmup, a.graph, a.dump_outputs = wl, args.config_steps, 5, -1, None
             t0 = time.perf_counter()
             sub = run_c5(a) if wl == "c5" else run_small(a)
             sub["run_s"] = round(time.perf_counter() - t0, 1)
             out[wl] = sub
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.neighbors_line and args.attention == "nodes" and not args.force_dist:
+    if extras and args.neighbors_line and args.attention == "nodes" and not args.force_dist:
         out["neighbors"] = neighbors_line(args)
     if rank == 0:
         emit(out)

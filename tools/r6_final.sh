@@ -6,31 +6,32 @@
 # smoke().  Every GPU step under its own time limit; the first failure ends the script.
 # Usage (via gpurun): bash tools/r6_final.sh TAG
 set -o pipefail
+O=${U2GNN_OUT:-bench_out}   # output directory, relative to the repository root
 TAG=${1:-r6f}
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out profiles/r06; export TMPDIR=/tmp
-timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/${TAG}_tests.log 2>&1
-rc=$?; echo "tests rc=$rc" >> gpurun_out/${TAG}_tests.log; tail -3 gpurun_out/${TAG}_tests.log
+R=${U2GNN_ROOT:-$(pwd)}; cd "$R"; mkdir -p $O profiles/r06; export TMPDIR=/tmp
+timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/${TAG}_tests.log 2>&1
+rc=$?; echo "tests rc=$rc" >> $O/${TAG}_tests.log; tail -3 $O/${TAG}_tests.log
 [ $rc -eq 0 ] || exit 1
-PCMD="python bench.py --steps 30 --warmup 5 --cpu-baseline 0 --fp32-steps 0 --pipeline-steps 0 --configs 0"
-GPU_MAX_HW_QUEUES=8 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/${TAG}_prof" -o run -- $PCMD > gpurun_out/${TAG}_prof.log 2>&1 || { echo "prof failed"; tail -5 gpurun_out/${TAG}_prof.log; exit 1; }
-DB=$(find "$R/gpurun_out/${TAG}_prof" -name '*.db' | head -1)
-python tools/kstats.py "$DB" gpurun_out/${TAG}_kstats.txt "$TAG $PCMD (rocprofv3 --kernel-trace --stats)" gpurun_out/${TAG}_ktrace.csv > /dev/null || exit 1
-python tools/timeline.py gpurun_out/${TAG}_ktrace.csv 5 > gpurun_out/${TAG}_timeline.txt || exit 1
-rm -rf "$R/gpurun_out/${TAG}_prof"
+PCMD="python bench.py --full --steps 30 --warmup 5 --cpu-baseline 0 --fp32-steps 0 --pipeline-steps 0 --configs 0"
+GPU_MAX_HW_QUEUES=8 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$O/${TAG}_prof" -o run -- $PCMD > $O/${TAG}_prof.log 2>&1 || { echo "prof failed"; tail -5 $O/${TAG}_prof.log; exit 1; }
+DB=$(find "$R/$O/${TAG}_prof" -name '*.db' | head -1)
+python tools/kstats.py "$DB" $O/${TAG}_kstats.txt "$TAG $PCMD (rocprofv3 --kernel-trace --stats)" $O/${TAG}_ktrace.csv > /dev/null || exit 1
+python tools/timeline.py $O/${TAG}_ktrace.csv 5 > $O/${TAG}_timeline.txt || exit 1
+rm -rf "$R/$O/${TAG}_prof"
 echo "c4 trace done"
 bash tools/gpu_pmc.sh $TAG || exit 1
-F=$(find "$R/gpurun_out/${TAG}_FETCH_SIZE" -name '*.db' | head -1)
-W=$(find "$R/gpurun_out/${TAG}_WRITE_SIZE" -name '*.db' | head -1)
-python tools/pmc_traffic.py "$F" "$W" gpurun_out/${TAG}_pmc_traffic.json > gpurun_out/${TAG}_pmc.log 2>&1 || { tail gpurun_out/${TAG}_pmc.log; exit 1; }
-rm -rf "$R/gpurun_out/${TAG}_FETCH_SIZE" "$R/gpurun_out/${TAG}_WRITE_SIZE"
+F=$(find "$R/$O/${TAG}_FETCH_SIZE" -name '*.db' | head -1)
+W=$(find "$R/$O/${TAG}_WRITE_SIZE" -name '*.db' | head -1)
+python tools/pmc_traffic.py "$F" "$W" $O/${TAG}_pmc_traffic.json > $O/${TAG}_pmc.log 2>&1 || { tail $O/${TAG}_pmc.log; exit 1; }
+rm -rf "$R/$O/${TAG}_FETCH_SIZE" "$R/$O/${TAG}_WRITE_SIZE"
 echo "pmc done"
 for WL in c5 c2 c3; do
-  bash tools/wl_trace.sh ${TAG}_$WL $WL > gpurun_out/${TAG}_${WL}_trace.log 2>&1 || { tail -5 gpurun_out/${TAG}_${WL}_trace.log; exit 1; }
+  bash tools/wl_trace.sh ${TAG}_$WL $WL > $O/${TAG}_${WL}_trace.log 2>&1 || { tail -5 $O/${TAG}_${WL}_trace.log; exit 1; }
 done
 echo "workload traces done"
-cp gpurun_out/${TAG}_kstats.json gpurun_out/${TAG}_pmc_traffic.json gpurun_out/${TAG}_c5_kstats.json \
-   gpurun_out/${TAG}_c2_kstats.json gpurun_out/${TAG}_c3_kstats.json profiles/r06/ || exit 1
-timeout -k 10 900 python bench.py --steps 30 --warmup 5 --cpu-baseline 1 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { echo "bench failed"; tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
+cp $O/${TAG}_kstats.json $O/${TAG}_pmc_traffic.json $O/${TAG}_c5_kstats.json \
+   $O/${TAG}_c2_kstats.json $O/${TAG}_c3_kstats.json profiles/r06/ || exit 1
+timeout -k 10 900 python bench.py --full --steps 30 --warmup 5 --cpu-baseline 1 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -20 $O/${TAG}_bench.err; exit 1; }
 echo "bench done"
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -5 gpurun_out/${TAG}_smoke.log; exit 1; }
-tail -1 gpurun_out/${TAG}_smoke.log
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1 || { tail -5 $O/${TAG}_smoke.log; exit 1; }
+tail -1 $O/${TAG}_smoke.log

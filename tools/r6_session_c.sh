@@ -1,15 +1,16 @@
 #!/usr/bin/env bash
 # Round-6 session C: fwd6 (unfused x6 attention) parity tests, then the full default bench line (fwd6) beside bf16x3
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out
+O=${U2GNN_OUT:-bench_out}   # output directory, relative to the repository root
+R=${U2GNN_ROOT:-$(pwd)}; cd "$R"; mkdir -p $O
 T="python -u -m pytest -x -q --timeout 300 --timeout-method thread"
-timeout -k 10 600 $T tests/test_train_parity_gpu.py tests/test_native_layer_gpu.py -k "fwd6" > gpurun_out/r6c_tests.log 2>&1 || { tail -30 gpurun_out/r6c_tests.log; exit 1; }
-tail -2 gpurun_out/r6c_tests.log
-timeout -k 10 500 python bench.py --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 > gpurun_out/r6c_bench.json 2> gpurun_out/r6c_bench.err || { tail -20 gpurun_out/r6c_bench.err; exit 1; }
-timeout -k 10 500 python bench.py --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 --fp32-steps 0 --precision bf16x3 > gpurun_out/r6c_bench_x3.json 2> gpurun_out/r6c_bench_x3.err || { tail -20 gpurun_out/r6c_bench_x3.err; exit 1; }
-python - <<'PY'
+timeout -k 10 600 $T tests/test_train_parity_gpu.py tests/test_native_layer_gpu.py -k "fwd6" > $O/r6c_tests.log 2>&1 || { tail -30 $O/r6c_tests.log; exit 1; }
+tail -2 $O/r6c_tests.log
+timeout -k 10 500 python bench.py --full --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 > $O/r6c_bench.json 2> $O/r6c_bench.err || { tail -20 $O/r6c_bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 --fp32-steps 0 --precision bf16x3 > $O/r6c_bench_x3.json 2> $O/r6c_bench_x3.err || { tail -20 $O/r6c_bench_x3.err; exit 1; }
+python - <<PY
 import json
-for f in ("gpurun_out/r6c_bench.json", "gpurun_out/r6c_bench_x3.json"):
+for f in ("$O/r6c_bench.json", "$O/r6c_bench_x3.json"):
     d = json.load(open(f))
     print(f, d["dtype"], d["ms_per_step"], d["value"])
     r = d.get("roofline") or {}

@@ -10,7 +10,7 @@ timeout -k 10 600 $T tests/test_gemm_h3_gpu.py tests/test_gemm_x6_gpu.py tests/t
 tail -1 gpurun_out/split_tests.log
 timeout -k 10 900 bash tools/ab.sh "base exp_oldsplit" > gpurun_out/split_ab.txt 2>&1 || { tail -20 gpurun_out/split_ab.txt; exit 1; }
 cat gpurun_out/split_ab.txt
-timeout -k 10 400 python bench.py --configs 0 --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 --neighbors-line 0 \
+timeout -k 10 400 python bench.py --full --configs 0 --steps 30 --warmup 5 --cpu-baseline 0 --pipeline-steps 0 --neighbors-line 0 \
   --no-roofline > gpurun_out/split_bench.json 2> gpurun_out/split_bench.err || { tail -20 gpurun_out/split_bench.err; exit 1; }
 python -c "
 import json;d=json.load(open('gpurun_out/split_bench.json'));print('fwdh', d['ms_per_step'], d['final_loss'], {k:(d[k]['ms_per_step'], d[k]['final_loss']) for k in ('bf16x3','fwd6','fwd32','fp32')})"
