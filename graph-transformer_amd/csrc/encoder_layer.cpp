@@ -43,10 +43,15 @@ struct Dims {
     int prec_fwd;  // forward products (U2GNN_LAYER_FWD_F32: exact fp32; U2GNN_LAYER_FWD_X6: bf16x6)
     bool deep_wgrad;
     int window;   // 0: attention over all N rows; W: within windows of W rows (N % W == 0)
+    // per-graph attention (u2gnn_layer_*_seg): n_seg > 0 consecutive row segments, offsets on the device (null
+    // while planning: the sizes depend on n_seg > 0 only)
+    const int64_t *seg = nullptr;
+    int n_seg = 0;
 };
 
-Dims make_dims(const u2gnn_layer_dims *a) {
+Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg = nullptr, int n_seg = 0) {
     Dims D;
+    D.seg = seg, D.n_seg = n_seg;
     D.N = a->N;
     D.d = a->d;
     D.ff = a->ff;
@@ -104,15 +109,17 @@ struct Ctx {   // tensors saved by the forward for the backward
     // Pd: with dropout the signed probability image (P/(1-p) where kept, -P where dropped), else P
     float *QKV, *Pd, *O, *Z1, *X1, *mean1, *rstd1, *Hd, *Z2, *mean2, *rstd2;
     float *Psave;   // window mode: [N/W, W, W] probabilities
-    float *stats;   // small-width node attention (d <= 32): its context (row statistics + compact Q, K, V)
+    // small-width node attention (d <= 32): its context (row statistics + compact Q, K, V); per-graph attention:
+    // the rows' (max, 1 / sum exp) pairs, [Np][2]
+    float *stats;
 };
 
 // node attention for d <= 32 on the vector ALUs (u2gnn_attn_small_*, small_layer.hip): every precision, no
 // N x N image (engine.small_attn mirrors the rule)
-bool small_attn(const Dims &D) { return !D.window && D.d <= 32; }
+bool small_attn(const Dims &D) { return !D.window && !D.n_seg && D.d <= 32; }
 // the forward tail (a3.3 + a3.4) of a mid-width layer with few rows as one row-block kernel + the slab LayerNorm
 // (mid_layer.hip; C2: 2 launches instead of 5); engine.mid_tail mirrors the rule
-bool mid_tail(const Dims &D) { return !D.window && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
+bool mid_tail(const Dims &D) { return !D.window && !D.n_seg && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
 
 Ctx carve_ctx(Arena &A, const Dims &D, bool drop) {
     Ctx c;
@@ -122,6 +129,8 @@ Ctx carve_ctx(Arena &A, const Dims &D, bool drop) {
     c.Pd = c.Psave = c.stats = nullptr;
     if (D.window)
         c.Psave = A.take<float>(D.N * D.window);
+    else if (D.n_seg)
+        c.stats = A.take<float>(2 * D.Np);
     else if (small_attn(D))
         c.stats = A.take<float>(u2gnn_attn_small_ctx_floats(D.Np, D.d));
     else
@@ -515,7 +524,7 @@ bool fused_attn(const Dims &D) {
 #ifndef U2GNN_EXP_FUSED_ANY_NP   // (A/B: the fused form at every row count, as up to r6i)
     if (D.Np < kFusedMinNp) return false;
 #endif
-    return !D.window && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 && D.prec_fwd != U2GNN_PREC_BF16X6 &&
+    return !D.window && !D.n_seg && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 && D.prec_fwd != U2GNN_PREC_BF16X6 &&
            D.dp <= 384;
 }
 
@@ -574,6 +583,11 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         if (!plan)
             U2GNN_TRY(u2gnn_window_attn_fwd(c.QKV, 3 * dp, D.window, (int32_t)dp, c.O, dp, c.Psave, pd, s->attn,
                                             N / D.window, Np, st));
+    } else if (D.n_seg) {
+        // per-graph attention: every row over the rows of its own segment (segment_attn.hip), exact fp32
+        if (!plan)
+            U2GNN_TRY(u2gnn_segment_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dp, c.stats, pd, s->attn,
+                                             N, Np, st));
     } else if (small_attn(D)) {
         // d <= 32: the whole layer on the vector ALUs (small_layer.hip): in-projection, softmax -> dropout -> P.V
         // flash-style (the row statistics and a compact Q, K, V saved) and a3.3 + a3.4 -- 2 or 3 launches
@@ -710,7 +724,7 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     float *ws = W.take<float>(colstat_ws_floats(N, dp));
     const bool tail = small_attn(D);   // the row-local tail kernel (small_layer.hip) forms dX1 ... dO and delta
     // one-stream layers in the matrix-core precisions: LayerNorm1's backward forms delta = rowsum(dO * O)
-    const bool ln_delta = !D.window && prec != U2GNN_PREC_F32;
+    const bool ln_delta = !D.window && !D.n_seg && prec != U2GNN_PREC_F32;
     float *dX1 = W.take<float>(Np * dp), *dF = W.take<float>(Np * dp);
     float *dH = W.take<float>(Np * ffp);
     float *dA = W.take<float>(Np * dp);
@@ -797,6 +811,13 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         if (!plan)
             U2GNN_TRY(u2gnn_window_attn_bwd(c.QKV, 3 * dp, D.window, (int32_t)dp, dO, dp, c.Psave, pd, s->attn,
                                             q_scale, dQKV, 3 * dp, N / D.window, Np, st));
+    } else if (D.n_seg) {
+        // per-graph attention: delta, dQ over query tiles, then dK, dV over key tiles (P recomputed from the statistics)
+        dQKV = W.take<float>(Np * 3 * dp);
+        float *seg_delta = W.take<float>(Np);
+        if (!plan)
+            U2GNN_TRY(u2gnn_segment_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dO, dp, c.stats, pd,
+                                             s->attn, q_scale, dQKV, 3 * dp, seg_delta, N, Np, st));
     } else if (small_attn(D)) {
         // d <= 32: dQ, dK, dV (P recomputed from the row statistics) and dX += dQKV W_in, run with the tail above
         dQKV = small_dqkv;
@@ -863,14 +884,21 @@ bool dims_ok(const u2gnn_layer_dims *a) {
            a->window >= 0 && a->window <= 32 && (a->window == 0 || a->N % a->window == 0);
 }
 
+// per-graph attention arguments: both or neither (neither = the node-axis layer), never with window mode
+bool seg_ok(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg) {
+    if (!seg && n_seg == 0) return true;
+    return seg && n_seg >= 1 && a->window == 0;
+}
+
 }  // namespace
 
 extern "C" {
 
-int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_bytes, int64_t *fwd_ws_bytes,
-                      int64_t *bwd_ws_bytes) {
+int u2gnn_layer_sizes_seg(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t *ctx_bytes,
+                          int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes) {
     if (!dims_ok(dims) || !ctx_bytes || !fwd_ws_bytes || !bwd_ws_bytes) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims);
+    if (n_seg < 0 || (n_seg && dims->window)) return U2GNN_E_ARG;
+    const Dims D = make_dims(dims, nullptr, n_seg);
     u2gnn_layer_seeds s;
     std::memset(&s, 0, sizeof(s));
     s.p_drop = p_drop;
@@ -887,11 +915,17 @@ int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_b
     return U2GNN_OK;
 }
 
-int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                    const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
-                    void *stream) {
+int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_bytes, int64_t *fwd_ws_bytes,
+                      int64_t *bwd_ws_bytes) {
+    return u2gnn_layer_sizes_seg(dims, p_drop, 0, ctx_bytes, fwd_ws_bytes, bwd_ws_bytes);
+}
+
+int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                        const int64_t *seg_offsets, int32_t n_seg, void *stream) {
     if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims);
+    if (!seg_ok(dims, seg_offsets, n_seg)) return U2GNN_E_ARG;
+    const Dims D = make_dims(dims, seg_offsets, n_seg);
     // the same call in planning mode first: a workspace or ctx arena smaller than this call takes is
     // refused before anything is launched (never a launch over the end of a caller buffer)
     Arena Pc(nullptr, 0), Pw(nullptr, 0);
@@ -902,11 +936,19 @@ int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, c
     return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                    const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
-                    const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, void *stream, void *side_stream) {
+int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                    const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                    void *stream) {
+    return u2gnn_layer_fwd_seg(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, nullptr, 0, stream);
+}
+
+int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                        int32_t n_seg, void *stream, void *side_stream) {
     if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims);
+    if (!seg_ok(dims, seg_offsets, n_seg)) return U2GNN_E_ARG;
+    const Dims D = make_dims(dims, seg_offsets, n_seg);
     Arena Pc(nullptr, 0), Pw(nullptr, 0);   // planning pass with this call's schedule (see u2gnn_layer_fwd)
     layer_bwd(D, w, s, X, Pc, dX2, dX, g, Pw, reinterpret_cast<hipStream_t>(stream),
               reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
@@ -915,6 +957,13 @@ int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, c
     Arena C(const_cast<void *>(ctx), ctx_bytes), W(ws ? ws : empty_ws, ws ? ws_bytes : 0);
     return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
+}
+
+int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                    const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                    const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, void *stream, void *side_stream) {
+    return u2gnn_layer_bwd_seg(dims, w, s, X, ctx, ctx_bytes, dX2, dX, g, ws, ws_bytes, nullptr, 0, stream,
+                               side_stream);
 }
 
 int u2gnn_probe_arm(int32_t role, int32_t capacity) {

@@ -14,14 +14,17 @@ u2gnn_hip.engine.MIXED_BF16_ROLES), "fwd32" (exact fp32 forward products, bf16x3
 forward's ReLU decisions carry fp32 rounding only), "fwd6" (the forward products on the
 three-plane bf16x6 split -- fp32-accurate products on bf16 matrix cores -- bf16x3 backward) or "bf16" (experiments
 only); ``attention`` = "nodes" (the fork's semantics: the encoder's sequence axis is
-the node axis, pytorch_U2GNN_Sup.py:35) or "neighbors" (the paper / TF semantics: each node
-attends over its own k+1 sampled neighbours, U2GNN_tf/model_U2GNN_Sup_multi.py:14-45).
+the node axis, pytorch_U2GNN_Sup.py:35), "neighbors" (the paper / TF semantics: each node
+attends over its own k+1 sampled neighbours, U2GNN_tf/model_U2GNN_Sup_multi.py:14-45) or "graphs"
+(the "nodes" encoder applied to every graph on its own: a node attends over the nodes of its graph,
+so a graph's scores do not depend on the other graphs of the batch; it needs each graph's nodes as
+consecutive rows, which ``forward`` checks on its graph_pool).
 """
 import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from u2gnn_hip.core import DeviceBatch, FlatParams, SupCore
+from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, FlatParams, SupCore
 
 
 class _SupFunction(torch.autograd.Function):
@@ -52,8 +55,8 @@ class TransformerU2GNN(nn.Module):
         self.num_U2GNN_layers = num_U2GNN_layers
         self.dropout_p = dropout
         self.precision = precision
-        if attention not in ("nodes", "neighbors"):
-            raise ValueError(f"attention must be 'nodes' or 'neighbors', got {attention!r}")
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
         self.attention = attention
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()

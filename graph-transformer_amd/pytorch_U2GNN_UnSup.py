@@ -12,6 +12,10 @@ outputs of every U2GNN layer -> dropout -> SampledSoftmax(vocab, sampled_num, d*
 pieces (cross-layer ``self_attn`` and the ``weight`` table it multiplies) are still constructed so
 fork state_dicts load, but they are not on the loss path (node-level research, OUT of scope), and
 ``sampler_type``/``loss_type`` other than 'default' raise NotImplementedError.
+
+Extra keyword ``attention``: "nodes" (the fork: attention over all nodes of the batch), "neighbors" (the paper:
+each node over its k+1 sampled neighbours) or "graphs" (each node over the nodes of its own graph; the batch must
+be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`` / ``from_store`` build them).
 """
 import math
 
@@ -21,7 +25,7 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from sampled_softmax import SampledSoftmax
 from u2gnn_hip import kernels as K
-from u2gnn_hip.core import DeviceBatch
+from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch
 from u2gnn_hip.engine import site_seed
 from u2gnn_hip.unsup import SITE_SS_DROP, UnSupCore
 
@@ -68,8 +72,8 @@ class TransformerU2GNN(nn.Module):
             raise NotImplementedError("only sampler_type='default', loss_type='default' (graph-level U2GNN) "
                                       "are on the MI355X path; neighbour/contrastive/gae are node-level research")
         self.feature_dim_size = feature_dim_size
-        if attention not in ("nodes", "neighbors"):
-            raise ValueError(f"attention must be 'nodes' or 'neighbors', got {attention!r}")
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
         self.attention = attention
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size

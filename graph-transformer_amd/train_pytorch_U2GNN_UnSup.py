@@ -47,9 +47,10 @@ parser.add_argument('--fold_idx', type=int, default=1, help='The fold index. 0-9
 parser.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "mixed", "bf16", "fwd32", "fwd6", "fwdh"],
                     help="matrix-core precision (MI355X): fp32 exact, bf16x3 split-bf16 (~fp32), mixed (bf16x3 "
                          "with the attention-backward dS/dQ/dK products in bf16), bf16")
-parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors"],
+parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors", "graphs"],
                     help="nodes = the fork's attention over all nodes of the batch; neighbors = the paper's "
-                         "attention over each node's k+1 sampled neighbours")
+                         "attention over each node's k+1 sampled neighbours; graphs = each node attends over "
+                         "the nodes of its own graph, so a graph's output does not depend on its batch")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
                     help="data-parallel ranks, one per GPU (started here under torch.distributed.run unless a "

@@ -63,6 +63,10 @@ class DeviceBatch:
     # True when colidx is 0..N-1 in order (batches built from offsets, _pool_iota): the pool backward
     # then stores every row of its output (u2gnn_pool_bwd_rows) instead of accumulating into zeros
     block_rows: bool = False
+    # True when graph g's nodes are the consecutive rows rowptr[g] .. rowptr[g+1]-1 (colidx is 0..N-1 in order):
+    # what attention="graphs" needs, since its segments are rowptr.  from_offsets / from_store build such batches;
+    # from_reference_inputs checks its graph_pool
+    rows_contiguous: bool = False
 
     def __post_init__(self):
         if self.err is None:
@@ -91,7 +95,8 @@ class DeviceBatch:
         lab = None if labels is None else torch.as_tensor(labels, dtype=torch.int64).to(dev, non_blocking=True)
         iy = None if input_y is None else torch.as_tensor(input_y, dtype=torch.int64).to(dev, non_blocking=True)
         return DeviceBatch(N, B, ix, X, off.to(dev), torch.arange(N, device=dev, dtype=torch.int64),
-                           torch.ones(N, device=dev, dtype=torch.float32), lab, iy, block_rows=True)
+                           torch.ones(N, device=dev, dtype=torch.float32), lab, iy, block_rows=True,
+                           rows_contiguous=True)
 
     @staticmethod
     def from_store(hb, X_dev: torch.Tensor, device="cuda"):
@@ -129,7 +134,7 @@ class DeviceBatch:
                 t.record_stream(main)
             iy = gnode if hb.input_y is not None else None
             colidx, vals = _pool_iota(N, dev)
-            return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True)
+            return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True, rows_contiguous=True)
         if slot is not None:
             k1 = hb.input_x.shape[1]
             h2d = lambda t: t.to(dev, non_blocking=True)  # noqa: E731
@@ -148,7 +153,7 @@ class DeviceBatch:
         if N:
             K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
         colidx, vals = _pool_iota(N, dev)
-        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True)
+        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True)
 
     @staticmethod
     def from_reference_inputs(input_x, graph_pool, X_concat, labels=None):
@@ -163,8 +168,12 @@ class DeviceBatch:
         vals = gp.values().to(torch.float32)
         rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
         rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=B), 0)
+        # graph g's nodes as consecutive rows (attention="graphs"): the coalesced pool lists every column once, in
+        # order (this constructor synchronises already)
+        contiguous = cols.numel() == int(N) and bool(
+            torch.equal(cols, torch.arange(int(N), device=cols.device, dtype=cols.dtype)))
         return DeviceBatch(int(N), int(B), input_x.to(dev).contiguous(), X_concat.to(torch.float32).contiguous(),
-                           rowptr, cols.contiguous(), vals.contiguous(), labels)
+                           rowptr, cols.contiguous(), vals.contiguous(), labels, rows_contiguous=contiguous)
 
 
 def _check_range_host(input_x, N: int):
@@ -174,6 +183,9 @@ def _check_range_host(input_x, N: int):
         raise IndexError("index out of range in self (input_x entry outside [0, N))")
 
 
+ATTENTION_MODES = ("nodes", "neighbors", "graphs")
+
+
 class EncoderStack:
     """L U2GNN layers x T post-LN encoder layers on slot-0 rows, with the re-gather between
     U2GNN layers (pytorch_U2GNN_Sup.py:33-39; pytorch_U2GNN_UnSup.py:55-64)."""
@@ -181,8 +193,8 @@ class EncoderStack:
     def __init__(self, u2gnn_layers, d: int, ff: int, T: int, L: int, prec: str = "fp32", p_enc: float = 0.5,
                  attention: str = "nodes"):
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
-        if attention not in ("nodes", "neighbors"):
-            raise ValueError(f"attention must be 'nodes' or 'neighbors', got {attention!r}")
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
         self.attention = attention
         self.packed = None
         # optional callable(prefix, stream): called once a layer's parameter gradients are
@@ -205,6 +217,16 @@ class EncoderStack:
         """Returns (outs, ctx): outs[l] = padded [Np, dp] slot-0 output of U2GNN layer l."""
         if self.attention == "neighbors":
             return self._forward_neighbors(b, train, need_ctx, seed)
+        # "graphs": the "nodes" path with every layer's attention cut into the batch's graphs (b.rowptr, on the device)
+        segments = None
+        if self.attention == "graphs":
+            if not native.enabled():
+                raise NotImplementedError("per-graph attention runs on the native layer executor (U2GNN_NATIVE_LAYER=1)")
+            if not b.rows_contiguous:
+                raise ValueError("attention='graphs' needs every graph's nodes as consecutive rows: graph_pool row g "
+                                 "must hold the columns rowptr[g] .. rowptr[g+1]-1 and colidx must be 0..N-1 in order "
+                                 "(DeviceBatch.from_offsets / from_store build such batches)")
+            segments = b.rowptr[:b.B + 1].contiguous()
         dev = b.X_concat.device
         d, dp = self.d, rup(self.d, 64)
         dims = Dims(b.N, d, self.ff)
@@ -219,7 +241,8 @@ class EncoderStack:
                 seeds = {s: site_seed(seed, l, t, s) for s in (SITE_ATTN, SITE_DROP1, SITE_DROPFF, SITE_DROP2)}
                 if native.enabled():
                     X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
-                                                need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad())
+                                                need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(),
+                                                segments=segments)
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                  need_ctx, self.prec, self.p_enc)

@@ -270,6 +270,31 @@ def window_attn_bwd(QKV, W, dp, dO, Psave, p, seed, q_scale, dQKV, n_nodes, rows
                                           int(n_nodes), int(rows_pad), _s()), "u2gnn_window_attn_bwd")
 
 
+def segment_attn_fwd(QKV, dp, seg_offsets, O, stats, p, seed, N, rows_pad):
+    """Per-graph attention: row i attends over the rows of its own segment (seg_offsets: int64 device [n_seg+1]);
+    QKV [rows_pad, >=3dp] = [Q/sqrt(d) | K | V]; stats [rows_pad, 2] receives (max, 1 / sum exp) per row."""
+    _dev(QKV, seg_offsets, O, stats)
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous():
+        raise _lib.U2GNNNativeError("segment offsets: a contiguous int64 device tensor")
+    check(hip_lib().u2gnn_segment_attn_fwd(_p(QKV), QKV.stride(0), int(dp), _p(seg_offsets), seg_offsets.numel() - 1,
+                                           _p(O), O.stride(0), _p(stats), float(p), int(seed), int(N), int(rows_pad),
+                                           _s()), "u2gnn_segment_attn_fwd")
+
+
+def segment_attn_bwd(QKV, dp, seg_offsets, O, dO, stats, p, seed, q_scale, dQKV, N, rows_pad):
+    """dQKV = [q_scale * dL/dQs | dL/dK | dL/dV] from the forward's O and stats (P is recomputed)."""
+    _dev(QKV, seg_offsets, O, dO, stats, dQKV)
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous():
+        raise _lib.U2GNNNativeError("segment offsets: a contiguous int64 device tensor")
+    if O.stride(0) != dO.stride(0):
+        raise _lib.U2GNNNativeError("O and dO share one leading dimension")
+    ws = torch.empty(int(rows_pad), device=QKV.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_segment_attn_bwd(_p(QKV), QKV.stride(0), int(dp), _p(seg_offsets), seg_offsets.numel() - 1,
+                                           _p(O), _p(dO), dO.stride(0), _p(stats), float(p), int(seed), float(q_scale),
+                                           _p(dQKV), dQKV.stride(0), _p(ws), int(N), int(rows_pad), _s()),
+          "u2gnn_segment_attn_bwd")
+
+
 def rowdot(A, lda, B, ldb, out, rows, cols):
     _dev(A, B, out)
     check(hip_lib().u2gnn_rowdot(_p(A), int(lda), _p(B), int(ldb), _p(out), int(rows), int(cols), _s()),

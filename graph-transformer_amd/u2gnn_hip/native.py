@@ -51,14 +51,20 @@ def _dims(N: int, d: int, ff: int, prec: str, deep_wgrad: bool, window: int = 0)
     return LayerDims(int(N), int(d), int(ff), PREC[prec], flags, int(window), 0)
 
 
-def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = True, window: int = 0):
-    key = (N, d, ff, prec, p_drop > 0, deep_wgrad, window)
+def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = True, window: int = 0,
+          segments: bool = False):
+    """segments: the per-graph attention layer (the sizes depend on the mode only, never on the offsets)."""
+    key = (N, d, ff, prec, p_drop > 0, deep_wgrad, window, bool(segments))
     r = _SIZES.get(key)
     if r is None:
         c, f, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         dims = _dims(N, d, ff, prec, deep_wgrad, window)
-        check(hip_lib().u2gnn_layer_sizes(ctypes.byref(dims), float(p_drop), ctypes.byref(c), ctypes.byref(f),
-                                          ctypes.byref(b)), "u2gnn_layer_sizes")
+        if segments:
+            check(hip_lib().u2gnn_layer_sizes_seg(ctypes.byref(dims), float(p_drop), 1, ctypes.byref(c),
+                                                  ctypes.byref(f), ctypes.byref(b)), "u2gnn_layer_sizes_seg")
+        else:
+            check(hip_lib().u2gnn_layer_sizes(ctypes.byref(dims), float(p_drop), ctypes.byref(c), ctypes.byref(f),
+                                              ctypes.byref(b)), "u2gnn_layer_sizes")
         r = _SIZES[key] = (c.value, f.value, b.value)
     return r
 
@@ -77,7 +83,17 @@ def _seeds(p_drop: float, seeds: Dict[int, int]) -> LayerSeeds:
 
 class NativeCtx:
     """What the backward needs from one layer's forward."""
-    __slots__ = ("X", "buf", "p_drop", "seeds", "window")
+    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments")
+
+
+def _segments(segments, dev):
+    """(pointer, count) of a per-graph attention layer's row offsets: int64 device [n_seg + 1]."""
+    if segments is None:
+        return None, 0
+    if (not segments.is_cuda or segments.device != dev or segments.dtype != torch.int64 or segments.dim() != 1
+            or segments.numel() < 2 or not segments.is_contiguous()):
+        raise _lib.U2GNNNativeError("segments: a contiguous int64 tensor [n_seg + 1] on the layer's device")
+    return ctypes.c_void_p(segments.data_ptr()), segments.numel() - 1
 
 
 def _stream(s=None):
@@ -85,40 +101,59 @@ def _stream(s=None):
 
 
 def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int, int], need_ctx: bool,
-                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0):
+                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None):
     """window = 0: attention over all dims.N rows; W: within each node's window of W token rows
-    (dims.N = nodes * W)."""
+    (dims.N = nodes * W).  segments (int64 device [n_seg + 1] row offsets): every row attends over the rows
+    of its own segment (per-graph attention); not together with window."""
     pd = p_enc if train else 0.0
-    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window)
+    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window, segments is not None)
     dev = X.device
     X2 = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32)
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
     dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(pd, seeds)
-    check(hip_lib().u2gnn_layer_fwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
-                                    X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                    ws.data_ptr(), ws.numel(), _stream()), "u2gnn_layer_fwd")
+    if segments is not None:
+        sp, ns = _segments(segments, dev)
+        check(hip_lib().u2gnn_layer_fwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
+                                            X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                            ws.data_ptr(), ws.numel(), sp, ns, _stream()), "u2gnn_layer_fwd_seg")
+    else:
+        check(hip_lib().u2gnn_layer_fwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
+                                        X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                        ws.data_ptr(), ws.numel(), _stream()), "u2gnn_layer_fwd")
     ctx = None
     if need_ctx:
         ctx = NativeCtx()
-        ctx.X, ctx.buf, ctx.p_drop, ctx.seeds, ctx.window = X, buf, pd, dict(seeds), window
+        ctx.X, ctx.buf, ctx.p_drop, ctx.seeds, ctx.window, ctx.segments = X, buf, pd, dict(seeds), window, segments
     return X2, ctx
 
 
 def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: str,
                    side: Optional["torch.cuda.Stream"] = None, deep_wgrad: bool = True,
-                   need_dx: bool = True) -> Optional[torch.Tensor]:
-    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, ctx.window)
+                   need_dx: bool = True, segments=None) -> Optional[torch.Tensor]:
+    """segments: None = the forward's (kept in ctx); given, it must be the forward's offsets."""
+    if segments is None:
+        segments = ctx.segments
+    elif ctx.segments is None:
+        raise _lib.U2GNNNativeError("layer_backward: segments given for a forward that ran without them")
+    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, ctx.window, segments is not None)
     dev = dX2.device
     dX = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32) if need_dx else None
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
     dd = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, ctx.window)
     pp, ss = _params(packed, p), _seeds(ctx.p_drop, ctx.seeds)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
-    check(hip_lib().u2gnn_layer_bwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
-                                    ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None, ctypes.byref(gg),
-                                    ws.data_ptr(), ws.numel(), _stream(), _stream(side) if side is not None else None),
-          "u2gnn_layer_bwd")
+    if segments is not None:
+        sp, ns = _segments(segments, dev)
+        check(hip_lib().u2gnn_layer_bwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
+                                            ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None,
+                                            ctypes.byref(gg), ws.data_ptr(), ws.numel(), sp, ns, _stream(),
+                                            _stream(side) if side is not None else None), "u2gnn_layer_bwd_seg")
+    else:
+        check(hip_lib().u2gnn_layer_bwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
+                                        ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None, ctypes.byref(gg),
+                                        ws.data_ptr(), ws.numel(), _stream(), _stream(side) if side is not None else None),
+              "u2gnn_layer_bwd")
     if side is not None:
         for t in (ws, ctx.buf, ctx.X, dX2):
             t.record_stream(side)

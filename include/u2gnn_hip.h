@@ -539,6 +539,30 @@ int u2gnn_window_attn_bwd(const float *QKV, int64_t ldq, int32_t W, int32_t dp, 
                           int64_t ldo, const float *Psave, float p, uint64_t seed, float q_scale,
                           float *dQKV, int64_t ldg, int64_t n_nodes, int64_t rows_pad, void *stream);
 
+/* ---- per-graph ("graphs" mode) attention: the node-axis attention of pytorch_U2GNN_Sup.py:19-21,35 applied to
+ * every graph of the mini-batch on its own (block-diagonal attention matrix) ------------------------------
+ * QKV [rows_pad, ldq >= 3dp] = [Q/sqrt(d) | K | V] as the in-projection writes it; segment g is rows
+ * seg_offsets[g] .. seg_offsets[g+1]-1 (seg_offsets: DEVICE int64 [n_seg+1], non-decreasing; never read by the
+ * host).  Row i of segment g: P_i = softmax over the keys j of segment g of Qs_i . K_j, Pd = keep(seed, i, j) ?
+ * P / (1-p) : 0 with the GLOBAL row i and column j (the matching block of the mask the node-axis path draws for
+ * this seed, and of u2gnn_dropout_mask(seed, N, N, p)), O_i = sum_j Pd_ij V_j.  stats [rows_pad][2] receives
+ * (max_j Qs_i . K_j, 1 / sum_j exp) per row -- what the backward recomputes P from; no [n_g, n_g] image exists and
+ * no bound applies to n_g.  Exact fp32 on the vector ALUs, no atomics (bit-identical from run to run).
+ * Any seg_offsets content is memory-safe: bounds are clamped to [0, N], empty segments are legal, and rows that no
+ * segment covers, as rows >= N, get zero output (all dp columns of every row < rows_pad are written).
+ * dp % 64 == 0; dp > 1024: U2GNN_E_SHAPE.  Null pointers, n_seg < 1, dp % 64 != 0, p outside [0, 1): U2GNN_E_ARG. */
+int u2gnn_segment_attn_fwd(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                           float *O, int64_t ldo, float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad,
+                           void *stream);
+/* dQKV [rows_pad, ldg >= 3dp] = [q_scale * dL/dQs | dL/dK | dL/dV] (every row < rows_pad written; rows >= N zero)
+ * from the forward's O and stats (unchanged) and dO [rows_pad, ldo]: delta_i = rowsum(dO_i * O_i), dS = P o (keep
+ * dPd / (1-p) - delta).  Two launches: query tiles (delta, dQ), then key tiles (dK, dV).  delta_ws: rows_pad
+ * floats of scratch. */
+int u2gnn_segment_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                           const float *O, const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed,
+                           float q_scale, float *dQKV, int64_t ldg, float *delta_ws, int64_t N, int64_t rows_pad,
+                           void *stream);
+
 /* ---- a3: one encoder layer (TransformerEncoderLayer(d, nhead=1, ff, dropout), post-LN, slot-0
  * rows) issued natively: forward and backward of pytorch_U2GNN_Sup.py:19-21,35 /
  * pytorch_U2GNN_UnSup.py:37-40,57, launch-for-launch the sequence of u2gnn_hip/engine.py.
@@ -599,6 +623,22 @@ int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w,
                     const u2gnn_layer_seeds *s, const float *X, const void *ctx, int64_t ctx_bytes,
                     const float *dX2, float *dX, const u2gnn_layer_grads *g, void *ws,
                     int64_t ws_bytes, void *stream, void *side_stream);
+/* The same three calls with per-graph attention (u2gnn_segment_attn_*; ABI 18 grew by these entry points, nothing
+ * else changed): seg_offsets (DEVICE int64 [n_seg+1]) cuts the N rows into n_seg consecutive segments and every row
+ * attends over its own segment.  The layer takes the generic route (in-projection GEMM -> segment attention ->
+ * out-projection and tail), the ctx arena holds the row statistics in place of the probability image, and the
+ * sizes depend on n_seg > 0 only, never on the offsets' values.  seg_offsets == NULL with n_seg == 0 is
+ * u2gnn_layer_fwd / u2gnn_layer_bwd exactly (u2gnn_layer_sizes_seg: n_seg == 0); one without the other, n_seg < 0,
+ * or segments together with dims->window: U2GNN_E_ARG before anything is launched. */
+int u2gnn_layer_sizes_seg(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t *ctx_bytes,
+                          int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes);
+int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                        const int64_t *seg_offsets, int32_t n_seg, void *stream);
+int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                        int32_t n_seg, void *stream, void *side_stream);
 
 /* ---- ABI v5: live launch timing of one product of the layer executor (diagnostics) ----
  * u2gnn_probe_arm(role, capacity) creates `capacity` pairs of timing events; every following
