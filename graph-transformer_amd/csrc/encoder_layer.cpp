@@ -47,7 +47,14 @@ struct Dims {
     // while planning: the sizes depend on n_seg > 0 only)
     const int64_t *seg = nullptr;
     int n_seg = 0;
+    // neighbour attention (u2gnn_layer_*_csr): csr_nnz > 0 entries of a CSR over the rows, arrays on the device (csr
+    // null while planning: the sizes depend on csr_nnz only)
+    const u2gnn_csr_attn *csr = nullptr;
+    int64_t csr_nnz = 0;
 };
+
+// attention over a row pattern (segments or a CSR): the generic route with a statistics-saving fp32 attention kernel
+bool sparse_attn(const Dims &D) { return D.n_seg || D.csr_nnz; }
 
 Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg = nullptr, int n_seg = 0) {
     Dims D;
@@ -116,10 +123,10 @@ struct Ctx {   // tensors saved by the forward for the backward
 
 // node attention for d <= 32 on the vector ALUs (u2gnn_attn_small_*, small_layer.hip): every precision, no
 // N x N image (engine.small_attn mirrors the rule)
-bool small_attn(const Dims &D) { return !D.window && !D.n_seg && D.d <= 32; }
+bool small_attn(const Dims &D) { return !D.window && !sparse_attn(D) && D.d <= 32; }
 // the forward tail (a3.3 + a3.4) of a mid-width layer with few rows as one row-block kernel + the slab LayerNorm
 // (mid_layer.hip; C2: 2 launches instead of 5); engine.mid_tail mirrors the rule
-bool mid_tail(const Dims &D) { return !D.window && !D.n_seg && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
+bool mid_tail(const Dims &D) { return !D.window && !sparse_attn(D) && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
 
 Ctx carve_ctx(Arena &A, const Dims &D, bool drop) {
     Ctx c;
@@ -129,7 +136,7 @@ Ctx carve_ctx(Arena &A, const Dims &D, bool drop) {
     c.Pd = c.Psave = c.stats = nullptr;
     if (D.window)
         c.Psave = A.take<float>(D.N * D.window);
-    else if (D.n_seg)
+    else if (sparse_attn(D))
         c.stats = A.take<float>(2 * D.Np);
     else if (small_attn(D))
         c.stats = A.take<float>(u2gnn_attn_small_ctx_floats(D.Np, D.d));
@@ -524,8 +531,8 @@ bool fused_attn(const Dims &D) {
 #ifndef U2GNN_EXP_FUSED_ANY_NP   // (A/B: the fused form at every row count, as up to r6i)
     if (D.Np < kFusedMinNp) return false;
 #endif
-    return !D.window && !D.n_seg && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 && D.prec_fwd != U2GNN_PREC_BF16X6 &&
-           D.dp <= 384;
+    return !D.window && !sparse_attn(D) && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 &&
+           D.prec_fwd != U2GNN_PREC_BF16X6 && D.dp <= 384;
 }
 
 // the row-local tail of a small-width layer (u2gnn_layer_tail_small_*, small_layer.hip): every precision when the
@@ -588,6 +595,11 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         if (!plan)
             U2GNN_TRY(u2gnn_segment_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dp, c.stats, pd, s->attn,
                                              N, Np, st));
+    } else if (D.csr_nnz) {
+        // neighbour attention: every row over the columns of its CSR row (csr_attn.hip), exact fp32
+        if (!plan)
+            U2GNN_TRY(u2gnn_csr_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.csr, c.O, dp, c.stats, pd, s->attn, N, Np,
+                                         st));
     } else if (small_attn(D)) {
         // d <= 32: the whole layer on the vector ALUs (small_layer.hip): in-projection, softmax -> dropout -> P.V
         // flash-style (the row statistics and a compact Q, K, V saved) and a3.3 + a3.4 -- 2 or 3 launches
@@ -724,7 +736,7 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     float *ws = W.take<float>(colstat_ws_floats(N, dp));
     const bool tail = small_attn(D);   // the row-local tail kernel (small_layer.hip) forms dX1 ... dO and delta
     // one-stream layers in the matrix-core precisions: LayerNorm1's backward forms delta = rowsum(dO * O)
-    const bool ln_delta = !D.window && !D.n_seg && prec != U2GNN_PREC_F32;
+    const bool ln_delta = !D.window && !sparse_attn(D) && prec != U2GNN_PREC_F32;
     float *dX1 = W.take<float>(Np * dp), *dF = W.take<float>(Np * dp);
     float *dH = W.take<float>(Np * ffp);
     float *dA = W.take<float>(Np * dp);
@@ -818,6 +830,14 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         if (!plan)
             U2GNN_TRY(u2gnn_segment_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dO, dp, c.stats, pd,
                                              s->attn, q_scale, dQKV, 3 * dp, seg_delta, N, Np, st));
+    } else if (D.csr_nnz) {
+        // neighbour attention: delta, the entries' Pd and dS and dQ per query row, then dK, dV per key row over the
+        // transpose (P recomputed from the statistics)
+        dQKV = W.take<float>(Np * 3 * dp);
+        float *edge_ws = W.take<float>(2 * D.csr_nnz);
+        if (!plan)
+            U2GNN_TRY(u2gnn_csr_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.csr, c.O, dO, dp, c.stats, pd, s->attn, q_scale,
+                                         dQKV, 3 * dp, edge_ws, N, Np, st));
     } else if (small_attn(D)) {
         // d <= 32: dQ, dK, dV (P recomputed from the row statistics) and dX += dQKV W_in, run with the tail above
         dQKV = small_dqkv;
@@ -890,15 +910,29 @@ bool seg_ok(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg) {
     return seg && n_seg >= 1 && a->window == 0;
 }
 
+// neighbour attention argument: none, or a complete CSR; never with window mode or with segments
+bool csr_ok(const u2gnn_layer_dims *a, int32_t n_seg, const u2gnn_csr_attn *A) {
+    if (!A) return true;
+    return A->rowptr && A->colidx && A->t_rowptr && A->t_src && A->t_eid && A->nnz >= 1 && a->window == 0 && n_seg == 0;
+}
+
+Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int n_seg, const u2gnn_csr_attn *A) {
+    Dims D = make_dims(a, seg, n_seg);
+    if (A) D.csr = A, D.csr_nnz = A->nnz;
+    return D;
+}
+
 }  // namespace
 
 extern "C" {
 
-int u2gnn_layer_sizes_seg(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t *ctx_bytes,
+int u2gnn_layer_sizes_csr(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t nnz, int64_t *ctx_bytes,
                           int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes) {
     if (!dims_ok(dims) || !ctx_bytes || !fwd_ws_bytes || !bwd_ws_bytes) return U2GNN_E_ARG;
     if (n_seg < 0 || (n_seg && dims->window)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, nullptr, n_seg);
+    if (nnz < 0 || (nnz && (dims->window || n_seg))) return U2GNN_E_ARG;
+    Dims D = make_dims(dims, nullptr, n_seg);
+    D.csr_nnz = nnz;
     u2gnn_layer_seeds s;
     std::memset(&s, 0, sizeof(s));
     s.p_drop = p_drop;
@@ -915,17 +949,22 @@ int u2gnn_layer_sizes_seg(const u2gnn_layer_dims *dims, float p_drop, int32_t n_
     return U2GNN_OK;
 }
 
+int u2gnn_layer_sizes_seg(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t *ctx_bytes,
+                          int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes) {
+    return u2gnn_layer_sizes_csr(dims, p_drop, n_seg, 0, ctx_bytes, fwd_ws_bytes, bwd_ws_bytes);
+}
+
 int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_bytes, int64_t *fwd_ws_bytes,
                       int64_t *bwd_ws_bytes) {
     return u2gnn_layer_sizes_seg(dims, p_drop, 0, ctx_bytes, fwd_ws_bytes, bwd_ws_bytes);
 }
 
-int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
-                        const int64_t *seg_offsets, int32_t n_seg, void *stream) {
+                        const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, void *stream) {
     if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    if (!seg_ok(dims, seg_offsets, n_seg)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg);
+    if (!seg_ok(dims, seg_offsets, n_seg) || !csr_ok(dims, n_seg, A)) return U2GNN_E_ARG;
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A);
     // the same call in planning mode first: a workspace or ctx arena smaller than this call takes is
     // refused before anything is launched (never a launch over the end of a caller buffer)
     Arena Pc(nullptr, 0), Pw(nullptr, 0);
@@ -936,19 +975,25 @@ int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
     return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
+int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                        const int64_t *seg_offsets, int32_t n_seg, void *stream) {
+    return u2gnn_layer_fwd_csr(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, seg_offsets, n_seg, nullptr, stream);
+}
+
 int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
                     const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
                     void *stream) {
     return u2gnn_layer_fwd_seg(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, nullptr, 0, stream);
 }
 
-int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
-                        int32_t n_seg, void *stream, void *side_stream) {
+                        int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream) {
     if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    if (!seg_ok(dims, seg_offsets, n_seg)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg);
+    if (!seg_ok(dims, seg_offsets, n_seg) || !csr_ok(dims, n_seg, A)) return U2GNN_E_ARG;
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A);
     Arena Pc(nullptr, 0), Pw(nullptr, 0);   // planning pass with this call's schedule (see u2gnn_layer_fwd)
     layer_bwd(D, w, s, X, Pc, dX2, dX, g, Pw, reinterpret_cast<hipStream_t>(stream),
               reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
@@ -957,6 +1002,14 @@ int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
     Arena C(const_cast<void *>(ctx), ctx_bytes), W(ws ? ws : empty_ws, ws ? ws_bytes : 0);
     return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
+}
+
+int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                        int32_t n_seg, void *stream, void *side_stream) {
+    return u2gnn_layer_bwd_csr(dims, w, s, X, ctx, ctx_bytes, dX2, dX, g, ws, ws_bytes, seg_offsets, n_seg, nullptr,
+                               stream, side_stream);
 }
 
 int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,

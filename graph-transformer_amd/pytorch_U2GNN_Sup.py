@@ -18,7 +18,10 @@ the node axis, pytorch_U2GNN_Sup.py:35), "neighbors" (the paper / TF semantics: 
 attends over its own k+1 sampled neighbours, U2GNN_tf/model_U2GNN_Sup_multi.py:14-45) or "graphs"
 (the "nodes" encoder applied to every graph on its own: a node attends over the nodes of its graph,
 so a graph's scores do not depend on the other graphs of the batch; it needs each graph's nodes as
-consecutive rows, which ``forward`` checks on its graph_pool).
+consecutive rows, which ``forward`` checks on its graph_pool) or "edges" (a node attends over itself and its
+graph neighbours: the batch's adjacency plus the diagonal, ``DeviceBatch.adj`` =
+``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``; structure-aware without sampling and, as "graphs",
+independent of the batch; reference-style tensor inputs carry no edges, so ``forward`` raises a ValueError for them).
 """
 import torch
 import torch.nn as nn
@@ -56,7 +59,7 @@ class TransformerU2GNN(nn.Module):
         self.dropout_p = dropout
         self.precision = precision
         if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
+            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()

@@ -15,7 +15,9 @@ fork state_dicts load, but they are not on the loss path (node-level research, O
 
 Extra keyword ``attention``: "nodes" (the fork: attention over all nodes of the batch), "neighbors" (the paper:
 each node over its k+1 sampled neighbours) or "graphs" (each node over the nodes of its own graph; the batch must
-be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`` / ``from_store`` build them).
+be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`` / ``from_store`` build them) or
+"edges" (each node over itself and its graph neighbours; the batch must be a ``DeviceBatch`` whose ``adj`` is
+``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``, else a ValueError).
 """
 import math
 
@@ -73,7 +75,7 @@ class TransformerU2GNN(nn.Module):
                                       "are on the MI355X path; neighbour/contrastive/gae are node-level research")
         self.feature_dim_size = feature_dim_size
         if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
+            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size

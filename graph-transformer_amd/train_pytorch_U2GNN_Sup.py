@@ -48,10 +48,13 @@ parser.add_argument('--fold_idx', type=int, default=1, help='The fold index. 0-9
 parser.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "mixed", "bf16", "fwd32", "fwd6", "fwdh"],
                     help="matrix-core precision (MI355X): fp32 exact, bf16x3 split-bf16 (~fp32), mixed (bf16x3 "
                          "with the attention-backward dS/dQ/dK products in bf16), bf16")
-parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors", "graphs"],
+parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors", "graphs", "edges"],
                     help="nodes = the fork's attention over all nodes of the batch; neighbors = the paper's "
                          "attention over each node's k+1 sampled neighbours; graphs = each node attends over "
-                         "the nodes of its own graph, so a graph's output does not depend on its batch")
+                         "the nodes of its own graph, so a graph's output does not depend on its batch; edges = "
+                         "each node attends over itself and its graph neighbours (the batch's adjacency, which "
+                         "the modes {nodes, neighbors, graphs} do not read; no sampling, and a graph's output "
+                         "does not depend on its batch either)")
 parser.add_argument("--autograd", action="store_true", help="reference loop: autograd + torch Adam/StepLR")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
@@ -68,7 +71,7 @@ if _rc is not None:
 
 from pytorch_U2GNN_Sup import TransformerU2GNN, label_smoothing  # noqa: E402
 from u2gnn_hip.batching import BatchLoader, GraphStore  # noqa: E402
-from u2gnn_hip.core import DeviceBatch  # noqa: E402
+from u2gnn_hip.core import Adjacency, DeviceBatch  # noqa: E402
 from u2gnn_hip.dp import GradAllReduce, OverlappedGradAllReduce, broadcast_params  # noqa: E402
 from u2gnn_hip.train import SupTrainer  # noqa: E402
 from util import load_data, separate_data  # noqa: E402
@@ -110,10 +113,14 @@ steps_per_epoch = -(-num_batches_per_epoch // run.world)
 train_X = torch.from_numpy(train_store.X).to(device)
 
 
-def to_device(hb):
+def to_device(hb, store=train_store):
     if hb.X_concat is None:
-        return DeviceBatch.from_store(hb, train_X, device=device)
-    return DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
+        b = DeviceBatch.from_store(hb, train_X, device=device)
+    else:
+        b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
+    if args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
+        b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
+    return b
 
 
 def cross_entropy(pred, soft_targets):
@@ -183,7 +190,7 @@ def evaluate():
                 continue
             # same numpy draws as the reference's get_batch_data on the test graphs (:178)
             hb = test_store.assemble(sampled_idx, args.num_neighbors)
-            prediction_output.append(model(to_device(hb), None, None).detach())
+            prediction_output.append(model(to_device(hb, test_store), None, None).detach())
     prediction_output = torch.cat(prediction_output, 0)
     predictions = prediction_output.max(1, keepdim=True)[1]
     labels = torch.LongTensor([graph.label for graph in test_graphs]).to(device)

@@ -47,10 +47,13 @@ parser.add_argument('--fold_idx', type=int, default=1, help='The fold index. 0-9
 parser.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "mixed", "bf16", "fwd32", "fwd6", "fwdh"],
                     help="matrix-core precision (MI355X): fp32 exact, bf16x3 split-bf16 (~fp32), mixed (bf16x3 "
                          "with the attention-backward dS/dQ/dK products in bf16), bf16")
-parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors", "graphs"],
+parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors", "graphs", "edges"],
                     help="nodes = the fork's attention over all nodes of the batch; neighbors = the paper's "
                          "attention over each node's k+1 sampled neighbours; graphs = each node attends over "
-                         "the nodes of its own graph, so a graph's output does not depend on its batch")
+                         "the nodes of its own graph, so a graph's output does not depend on its batch; edges = "
+                         "each node attends over itself and its graph neighbours (the batch's adjacency, which "
+                         "the modes {nodes, neighbors, graphs} do not read; no sampling, and a graph's output "
+                         "does not depend on its batch either)")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
                     help="data-parallel ranks, one per GPU (started here under torch.distributed.run unless a "
@@ -66,7 +69,7 @@ if _rc is not None:
 
 from pytorch_U2GNN_UnSup import TransformerU2GNN  # noqa: E402
 from u2gnn_hip.batching import BatchLoader, GraphStore  # noqa: E402
-from u2gnn_hip.core import DeviceBatch  # noqa: E402
+from u2gnn_hip.core import Adjacency, DeviceBatch  # noqa: E402
 from u2gnn_hip.dp import UnSupGradSync, broadcast_params, max_batch_nodes  # noqa: E402
 from u2gnn_hip.unsup import UnSupTrainer, fold_accuracies, graph_embeddings  # noqa: E402
 from util import load_data, separate_data_idx  # noqa: E402
@@ -126,6 +129,8 @@ def train():
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
         b = DeviceBatch.from_store(hb, store_X, device=device)
+        if args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
+            b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]
         sid = torch.from_numpy(draws[run.rank]).to(device)

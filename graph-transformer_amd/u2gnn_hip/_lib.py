@@ -107,6 +107,11 @@ class LayerGrads(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in _PKEYS]
 
 
+class CsrAttn(ctypes.Structure):
+    """u2gnn_csr_attn: the device arrays of a batch's attention pattern (core.Adjacency owns them)."""
+    _fields_ = [(k, c_void_p) for k in ("rowptr", "colidx", "t_rowptr", "t_src", "t_eid")] + [("nnz", c_int64)]
+
+
 _TAIL_PTRS = ("W_o", "b_o", "n1_w", "n1_b", "W1", "b1", "W2", "b2", "n2_w", "n2_b", "O", "X", "Z1", "X1", "mean1",
               "rstd1", "Hd", "Z2", "X2", "mean2", "rstd2", "dX2", "dX1", "dF", "dH", "dX", "dA", "dO", "delta")
 
@@ -157,6 +162,15 @@ _HIP_SIGS = {
                              VP, I32, VP], c_int32),
     "u2gnn_layer_bwd_seg": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,
                              POINTER(LayerGrads), VP, I64, VP, I32, VP, VP], c_int32),
+    "u2gnn_csr_attn_fwd": ([VP, I64, I32, POINTER(CsrAttn), VP, I64, VP, F32, c_uint64, I64, I64, VP], c_int32),
+    "u2gnn_csr_attn_bwd": ([VP, I64, I32, POINTER(CsrAttn), VP, VP, I64, VP, F32, c_uint64, F32, VP, I64, VP, I64, I64,
+                            VP], c_int32),
+    "u2gnn_layer_sizes_csr": ([POINTER(LayerDims), F32, I32, I64, POINTER(c_int64), POINTER(c_int64),
+                               POINTER(c_int64)], c_int32),
+    "u2gnn_layer_fwd_csr": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
+                             VP, I32, POINTER(CsrAttn), VP], c_int32),
+    "u2gnn_layer_bwd_csr": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,
+                             POINTER(LayerGrads), VP, I64, VP, I32, POINTER(CsrAttn), VP, VP], c_int32),
     "u2gnn_layer_sizes": ([POINTER(LayerDims), F32, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)], c_int32),
     "u2gnn_layer_fwd": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
                          VP], c_int32),

@@ -41,6 +41,17 @@ class HostBatch:
         return int(self.offsets[-1])
 
 
+def csr_with_self(N: int, rows: np.ndarray, cols: np.ndarray):
+    """(rowptr [N+1], colidx [nnz]), int64: the entries (rows[e], cols[e]) plus the diagonal, every row sorted by
+    column and without repeats."""
+    diag = np.arange(N, dtype=np.int64)
+    keys = np.unique(np.concatenate([np.asarray(rows, dtype=np.int64), diag]) * max(N, 1)
+                     + np.concatenate([np.asarray(cols, dtype=np.int64), diag]))
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys // max(N, 1), minlength=N), out=rowptr[1:])
+    return rowptr, np.ascontiguousarray(keys % max(N, 1))
+
+
 class GraphStore:
     """Per-dataset arrays: node features, labels, neighbour CSR in the reference's order."""
 
@@ -76,6 +87,23 @@ class GraphStore:
 
     def degrees_of(self, ids) -> np.ndarray:
         return np.concatenate([self.deg[self.node_start[i]:self.node_start[i + 1]] for i in ids])
+
+    def adjacency(self, graph_ids: Sequence[int]):
+        """(rowptr [N+1], colidx [nnz]), int64, of the batch ``graph_ids`` in the batch's row numbering (graph
+        ``graph_ids[g]`` = rows offsets[g] .. offsets[g+1]-1, as ``assemble`` lays them out): row i lists itself and
+        its graph neighbours, sorted and without repeats -- what attention="edges" attends over
+        (``core.Adjacency.from_csr``).  Deterministic: nothing is drawn from any RNG."""
+        ids = np.asarray(graph_ids, dtype=np.int64)
+        sizes = self.n_nodes[ids]
+        offsets = np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offsets[1:])
+        N = int(offsets[-1])
+        rowbase = np.repeat(offsets[:-1], sizes)                     # first batch row of each row's graph
+        gnode = np.repeat(self.node_start[ids], sizes) + (np.arange(N, dtype=np.int64) - rowbase)
+        deg = self.deg[gnode]
+        first = np.cumsum(deg) - deg                                 # each row's first entry in the batch's list
+        pos = np.repeat(self.nbr_start[gnode] - first, deg) + np.arange(int(deg.sum()), dtype=np.int64)
+        return csr_with_self(N, np.repeat(np.arange(N, dtype=np.int64), deg), self.nbr[pos] + np.repeat(rowbase, deg))
 
     def assemble(self, graph_ids: Sequence[int], num_neighbors: int, rng=np.random,
                  with_input_y: bool = False, gather_x: bool = True, out=None) -> HostBatch:

@@ -46,6 +46,49 @@ def _pool_iota(N: int, dev: torch.device):
     return c[0][:N], c[1][:N]
 
 
+class Adjacency:
+    """The attention pattern of attention="edges" on the device: row i attends over colidx[rowptr[i] .. rowptr[i+1])
+    (GraphStore.adjacency: the node itself and its graph neighbours), with the transpose the backward walks: for
+    column j the entries e = t_eid[t] (indices into colidx) and their rows t_src[t], t in t_rowptr[j] ..
+    t_rowptr[j+1].  Five int64 tensors and nnz; the kernels never hand them back to the host."""
+    __slots__ = ("N", "nnz", "rowptr", "colidx", "t_rowptr", "t_src", "t_eid", "_c")
+
+    def __init__(self, N, rowptr, colidx, t_rowptr, t_src, t_eid):
+        self.N, self.nnz = int(N), int(colidx.numel())
+        self.rowptr, self.colidx, self.t_rowptr, self.t_src, self.t_eid = rowptr, colidx, t_rowptr, t_src, t_eid
+        self._c = None
+
+    @staticmethod
+    def from_csr(rowptr, colidx, N: int, device="cuda") -> "Adjacency":
+        """Validates the CSR on the host (ValueError: rowptr not [N+1], not starting at 0, decreasing or not ending
+        at len(colidx); a column outside [0, N)), builds the transpose by a stable argsort of the columns (the
+        entries of a column keep their row order) and moves the five arrays to ``device``."""
+        rp = np.ascontiguousarray(np.asarray(rowptr), dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(np.asarray(colidx), dtype=np.int64).reshape(-1)
+        N = int(N)
+        if N < 1 or rp.shape[0] != N + 1:
+            raise ValueError(f"adjacency: rowptr must hold N + 1 = {N + 1} entries, got {rp.shape[0]}")
+        if rp[0] != 0 or rp[-1] != ci.shape[0] or (np.diff(rp) < 0).any():
+            raise ValueError("adjacency: rowptr must start at 0, never decrease and end at len(colidx)")
+        if ci.shape[0] and (ci.min() < 0 or ci.max() >= N):
+            raise ValueError(f"adjacency: a column index outside [0, {N})")
+        order = np.argsort(ci, kind="stable")                       # entry ids grouped by column, rows ascending
+        t_rowptr = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(np.bincount(ci, minlength=N), out=t_rowptr[1:])
+        rows = np.repeat(np.arange(N, dtype=np.int64), np.diff(rp))
+        dev = torch.device(device)
+        h2d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)  # noqa: E731
+        return Adjacency(N, h2d(rp), h2d(ci), h2d(t_rowptr), h2d(rows[order]), h2d(order))
+
+    def c_struct(self):
+        """The u2gnn_csr_attn of these arrays (kept alive with them)."""
+        if self._c is None:
+            from ._lib import CsrAttn
+            self._c = CsrAttn(*[t.data_ptr() or None for t in (self.rowptr, self.colidx, self.t_rowptr, self.t_src,
+                                                               self.t_eid)], self.nnz)
+        return self._c
+
+
 @dataclass
 class DeviceBatch:
     N: int
@@ -67,6 +110,9 @@ class DeviceBatch:
     # what attention="graphs" needs, since its segments are rowptr.  from_offsets / from_store build such batches;
     # from_reference_inputs checks its graph_pool
     rows_contiguous: bool = False
+    # the rows' attention pattern (attention="edges"): Adjacency.from_csr(*store.adjacency(graph_ids), N, device);
+    # the other modes never read it
+    adj: Optional[Adjacency] = None
 
     def __post_init__(self):
         if self.err is None:
@@ -183,7 +229,7 @@ def _check_range_host(input_x, N: int):
         raise IndexError("index out of range in self (input_x entry outside [0, N))")
 
 
-ATTENTION_MODES = ("nodes", "neighbors", "graphs")
+ATTENTION_MODES = ("nodes", "neighbors", "graphs", "edges")
 
 
 class EncoderStack:
@@ -194,7 +240,7 @@ class EncoderStack:
                  attention: str = "nodes"):
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
         if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors' or 'graphs', got {attention!r}")
+            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
         self.packed = None
         # optional callable(prefix, stream): called once a layer's parameter gradients are
@@ -227,6 +273,19 @@ class EncoderStack:
                                  "must hold the columns rowptr[g] .. rowptr[g+1]-1 and colidx must be 0..N-1 in order "
                                  "(DeviceBatch.from_offsets / from_store build such batches)")
             segments = b.rowptr[:b.B + 1].contiguous()
+        # "edges": the "nodes" path with every row attending over its row of the batch's adjacency (b.adj, on the device)
+        adjacency = None
+        if self.attention == "edges":
+            if not native.enabled():
+                raise NotImplementedError("neighbour attention over the adjacency runs on the native layer executor "
+                                          "(U2GNN_NATIVE_LAYER=1)")
+            if b.adj is None:
+                raise ValueError("attention='edges' needs the batch's adjacency: set DeviceBatch.adj = "
+                                 "Adjacency.from_csr(*store.adjacency(graph_ids), N, device) (reference-style tensor "
+                                 "inputs carry no edges)")
+            if b.adj.N != b.N:
+                raise ValueError(f"attention='edges': the adjacency is over {b.adj.N} rows, the batch has {b.N}")
+            adjacency = b.adj
         dev = b.X_concat.device
         d, dp = self.d, rup(self.d, 64)
         dims = Dims(b.N, d, self.ff)
@@ -242,7 +301,7 @@ class EncoderStack:
                 if native.enabled():
                     X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                 need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(),
-                                                segments=segments)
+                                                segments=segments, adjacency=adjacency)
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                  need_ctx, self.prec, self.p_enc)

@@ -295,6 +295,34 @@ def segment_attn_bwd(QKV, dp, seg_offsets, O, dO, stats, p, seed, q_scale, dQKV,
           "u2gnn_segment_attn_bwd")
 
 
+def _csr(adjacency, *tensors):
+    """The u2gnn_csr_attn of a core.Adjacency whose arrays live on the tensors' device."""
+    if adjacency is None or not adjacency.rowptr.is_cuda or adjacency.rowptr.device != tensors[0].device:
+        raise _lib.U2GNNNativeError("adjacency: a core.Adjacency on the tensors' device")
+    return ctypes.byref(adjacency.c_struct())
+
+
+def csr_attn_fwd(QKV, dp, adjacency, O, stats, p, seed, N, rows_pad):
+    """Neighbour attention: row i attends over the columns of its CSR row (adjacency: core.Adjacency on the device);
+    QKV [rows_pad, >=3dp] = [Q/sqrt(d) | K | V]; stats [rows_pad, 2] receives (max, 1 / sum exp) per row."""
+    _dev(QKV, O, stats)
+    check(hip_lib().u2gnn_csr_attn_fwd(_p(QKV), QKV.stride(0), int(dp), _csr(adjacency, QKV), _p(O), O.stride(0),
+                                       _p(stats), float(p), int(seed), int(N), int(rows_pad), _s()),
+          "u2gnn_csr_attn_fwd")
+
+
+def csr_attn_bwd(QKV, dp, adjacency, O, dO, stats, p, seed, q_scale, dQKV, N, rows_pad):
+    """dQKV = [q_scale * dL/dQs | dL/dK | dL/dV] from the forward's O and stats (P is recomputed)."""
+    _dev(QKV, O, dO, stats, dQKV)
+    if O.stride(0) != dO.stride(0):
+        raise _lib.U2GNNNativeError("O and dO share one leading dimension")
+    A = _csr(adjacency, QKV)
+    ws = torch.empty(2 * max(1, int(adjacency.nnz)), device=QKV.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_csr_attn_bwd(_p(QKV), QKV.stride(0), int(dp), A, _p(O), _p(dO), dO.stride(0), _p(stats),
+                                       float(p), int(seed), float(q_scale), _p(dQKV), dQKV.stride(0), _p(ws), int(N),
+                                       int(rows_pad), _s()), "u2gnn_csr_attn_bwd")
+
+
 def rowdot(A, lda, B, ldb, out, rows, cols):
     _dev(A, B, out)
     check(hip_lib().u2gnn_rowdot(_p(A), int(lda), _p(B), int(ldb), _p(out), int(rows), int(cols), _s()),

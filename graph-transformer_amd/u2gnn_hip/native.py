@@ -52,14 +52,19 @@ def _dims(N: int, d: int, ff: int, prec: str, deep_wgrad: bool, window: int = 0)
 
 
 def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = True, window: int = 0,
-          segments: bool = False):
-    """segments: the per-graph attention layer (the sizes depend on the mode only, never on the offsets)."""
-    key = (N, d, ff, prec, p_drop > 0, deep_wgrad, window, bool(segments))
+          segments: bool = False, nnz: int = 0):
+    """segments: the per-graph attention layer (the sizes depend on the mode only, never on the offsets); nnz > 0:
+    the neighbour attention layer over a CSR of nnz entries (its backward workspace holds 2 nnz floats)."""
+    key = (N, d, ff, prec, p_drop > 0, deep_wgrad, window, bool(segments), int(nnz))
     r = _SIZES.get(key)
     if r is None:
         c, f, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         dims = _dims(N, d, ff, prec, deep_wgrad, window)
-        if segments:
+        if nnz:
+            check(hip_lib().u2gnn_layer_sizes_csr(ctypes.byref(dims), float(p_drop), 1 if segments else 0, int(nnz),
+                                                  ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
+                  "u2gnn_layer_sizes_csr")
+        elif segments:
             check(hip_lib().u2gnn_layer_sizes_seg(ctypes.byref(dims), float(p_drop), 1, ctypes.byref(c),
                                                   ctypes.byref(f), ctypes.byref(b)), "u2gnn_layer_sizes_seg")
         else:
@@ -83,7 +88,14 @@ def _seeds(p_drop: float, seeds: Dict[int, int]) -> LayerSeeds:
 
 class NativeCtx:
     """What the backward needs from one layer's forward."""
-    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments")
+    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments", "adjacency")
+
+
+def _adjacency(adjacency, dev):
+    """The u2gnn_csr_attn of a neighbour attention layer's core.Adjacency (arrays on the layer's device)."""
+    if adjacency.nnz < 1 or not adjacency.rowptr.is_cuda or adjacency.rowptr.device != dev:
+        raise _lib.U2GNNNativeError("adjacency: a core.Adjacency with at least one entry on the layer's device")
+    return ctypes.byref(adjacency.c_struct())
 
 
 def _segments(segments, dev):
@@ -101,18 +113,26 @@ def _stream(s=None):
 
 
 def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int, int], need_ctx: bool,
-                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None):
+                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None, adjacency=None):
     """window = 0: attention over all dims.N rows; W: within each node's window of W token rows
     (dims.N = nodes * W).  segments (int64 device [n_seg + 1] row offsets): every row attends over the rows
-    of its own segment (per-graph attention); not together with window."""
+    of its own segment (per-graph attention); not together with window.  adjacency (core.Adjacency): every row
+    attends over the columns of its CSR row (neighbour attention); not together with window or segments."""
     pd = p_enc if train else 0.0
-    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window, segments is not None)
+    nnz = adjacency.nnz if adjacency is not None else 0
+    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window, segments is not None, nnz)
     dev = X.device
     X2 = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32)
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
     dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(pd, seeds)
-    if segments is not None:
+    if adjacency is not None:
+        sp, ns = _segments(segments, dev)
+        check(hip_lib().u2gnn_layer_fwd_csr(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
+                                            X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                            ws.data_ptr(), ws.numel(), sp, ns, _adjacency(adjacency, dev), _stream()),
+              "u2gnn_layer_fwd_csr")
+    elif segments is not None:
         sp, ns = _segments(segments, dev)
         check(hip_lib().u2gnn_layer_fwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
                                             X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
@@ -125,25 +145,38 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
     if need_ctx:
         ctx = NativeCtx()
         ctx.X, ctx.buf, ctx.p_drop, ctx.seeds, ctx.window, ctx.segments = X, buf, pd, dict(seeds), window, segments
+        ctx.adjacency = adjacency
     return X2, ctx
 
 
 def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: str,
                    side: Optional["torch.cuda.Stream"] = None, deep_wgrad: bool = True,
-                   need_dx: bool = True, segments=None) -> Optional[torch.Tensor]:
-    """segments: None = the forward's (kept in ctx); given, it must be the forward's offsets."""
+                   need_dx: bool = True, segments=None, adjacency=None) -> Optional[torch.Tensor]:
+    """segments / adjacency: None = the forward's (kept in ctx); given, it must be the forward's."""
+    if adjacency is None:
+        adjacency = ctx.adjacency
+    elif ctx.adjacency is None:
+        raise _lib.U2GNNNativeError("layer_backward: an adjacency given for a forward that ran without one")
     if segments is None:
         segments = ctx.segments
     elif ctx.segments is None:
         raise _lib.U2GNNNativeError("layer_backward: segments given for a forward that ran without them")
-    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, ctx.window, segments is not None)
+    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, ctx.window, segments is not None,
+                      adjacency.nnz if adjacency is not None else 0)
     dev = dX2.device
     dX = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32) if need_dx else None
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
     dd = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, ctx.window)
     pp, ss = _params(packed, p), _seeds(ctx.p_drop, ctx.seeds)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
-    if segments is not None:
+    if adjacency is not None:
+        sp, ns = _segments(segments, dev)
+        check(hip_lib().u2gnn_layer_bwd_csr(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
+                                            ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None,
+                                            ctypes.byref(gg), ws.data_ptr(), ws.numel(), sp, ns,
+                                            _adjacency(adjacency, dev), _stream(),
+                                            _stream(side) if side is not None else None), "u2gnn_layer_bwd_csr")
+    elif segments is not None:
         sp, ns = _segments(segments, dev)
         check(hip_lib().u2gnn_layer_bwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
                                             ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None,

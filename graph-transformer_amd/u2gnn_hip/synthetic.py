@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .batching import HostBatch
+from .batching import HostBatch, csr_with_self
 
 
 class SyntheticStore:
@@ -67,6 +67,18 @@ class SyntheticStore:
 
     def degrees_of(self, ids):
         return np.concatenate([self.graph(int(i))[2] for i in ids])
+
+    def adjacency(self, graph_ids):
+        """GraphStore.adjacency for the synthetic graphs: (rowptr, colidx) of the batch, every row itself plus its
+        neighbours, sorted and without repeats; nothing is drawn from any RNG."""
+        ids = np.asarray(graph_ids, dtype=np.int64)
+        parts = [self.graph(int(i)) for i in ids]
+        offsets = np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum(self.n_nodes[ids], out=offsets[1:])
+        N = int(offsets[-1])
+        deg = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, dtype=np.int64)
+        cols = np.concatenate([p[1] + offsets[j] for j, p in enumerate(parts)]) if parts else deg
+        return csr_with_self(N, np.repeat(np.arange(N, dtype=np.int64), deg), cols)
 
     def assemble(self, graph_ids, num_neighbors: int, rng=np.random, with_input_y: bool = False) -> HostBatch:
         ids = np.asarray(graph_ids, dtype=np.int64)

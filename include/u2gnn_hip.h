@@ -563,6 +563,34 @@ int u2gnn_segment_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const int6
                            float q_scale, float *dQKV, int64_t ldg, float *delta_ws, int64_t N, int64_t rows_pad,
                            void *stream);
 
+/* ---- neighbour ("edges" mode) attention: row i attends over the columns of its CSR row -- the batch's adjacency
+ * plus the diagonal when the caller builds it so (u2gnn_hip.core.Adjacency).  The conventions of
+ * u2gnn_segment_attn_*: QKV [rows_pad, ldq >= 3dp] = [Q/sqrt(d) | K | V]; P_i = softmax over the entries e of row
+ * i of Qs_i . K_col(e) (a column listed twice counts twice), Pd = keep(seed, i, j) ? P / (1-p) : 0 with the GLOBAL
+ * row i and column j (the entry of u2gnn_dropout_mask(seed, N, N, p)), O_i = sum_e Pd_e V_col(e); stats
+ * [rows_pad][2] receives (max, 1 / sum exp) per row.  Every row < rows_pad of O / dQKV is written: zeros for rows
+ * >= N and for rows with no entries.  Exact fp32 on the vector ALUs (a 16-lane group per row, online softmax: any
+ * row degree is legal), no atomics: bit-identical from run to run.
+ * All five arrays are DEVICE int64 and never read by the host (the calls capture into a HIP graph).  Any content
+ * is memory-safe: rowptr / t_rowptr values are clamped to [0, nnz], and entries with a column, source row or entry
+ * id out of range are skipped.  The forward reads rowptr and colidx only.
+ * dp % 64 == 0; dp > 1024: U2GNN_E_SHAPE.  Null pointers (A and the members a call reads), nnz < 1, dp % 64 != 0,
+ * p outside [0, 1): U2GNN_E_ARG before anything is launched. */
+typedef struct u2gnn_csr_attn {
+    const int64_t *rowptr, *colidx;          /* [N+1], [nnz]: row i attends over colidx[rowptr[i] .. rowptr[i+1]) */
+    const int64_t *t_rowptr, *t_src, *t_eid; /* the transpose: for column j the entries e = t_eid[t] (an index */
+    int64_t nnz;                             /* into colidx) and their rows t_src[t], t in t_rowptr[j] .. t_rowptr[j+1] */
+} u2gnn_csr_attn;
+int u2gnn_csr_attn_fwd(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_csr_attn *A, float *O, int64_t ldo,
+                       float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad, void *stream);
+/* dQKV [rows_pad, ldg >= 3dp] = [q_scale * dL/dQs | dL/dK | dL/dV] from the forward's O and stats (unchanged) and
+ * dO [rows_pad, ldo].  Two launches: per query row (delta_i = rowsum(dO_i * O_i); per entry e = (i, j): Pd_e and
+ * dS_e = P_e (keep dPd_e / (1-p) - delta_i) into edge_ws, dQ_i += dS_e K_j), then per key row j over the transpose
+ * (dK_j = sum dS_e Qs_src(e), dV_j = sum Pd_e dO_src(e)).  edge_ws: 2 * nnz floats of scratch. */
+int u2gnn_csr_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_csr_attn *A, const float *O,
+                       const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed, float q_scale,
+                       float *dQKV, int64_t ldg, float *edge_ws, int64_t N, int64_t rows_pad, void *stream);
+
 /* ---- a3: one encoder layer (TransformerEncoderLayer(d, nhead=1, ff, dropout), post-LN, slot-0
  * rows) issued natively: forward and backward of pytorch_U2GNN_Sup.py:19-21,35 /
  * pytorch_U2GNN_UnSup.py:37-40,57, launch-for-launch the sequence of u2gnn_hip/engine.py.
@@ -639,6 +667,22 @@ int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
                         int32_t n_seg, void *stream, void *side_stream);
+/* The same three calls with neighbour attention (u2gnn_csr_attn_*; ABI 18 grew by these entry points, nothing else
+ * changed): every row attends over the columns of its CSR row.  The layer takes the generic route (in-projection
+ * GEMM -> CSR attention -> out-projection and tail), the ctx arena holds the row statistics in place of the
+ * probability image, and the backward workspace grows by 2 * nnz floats (the entries' Pd and dS).  These are the
+ * general forms: they take the segment arguments of the _seg calls as well, and A == NULL (sizes: nnz == 0) is the _seg call with the same seg_offsets, n_seg exactly (the _seg calls forward here).  A with a NULL
+ * member or nnz < 1 (sizes: nnz < 0), A together with dims->window, or A together with segments (a layer takes one
+ * attention pattern): U2GNN_E_ARG before anything is launched. */
+int u2gnn_layer_sizes_csr(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t nnz, int64_t *ctx_bytes,
+                          int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes);
+int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                        const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, void *stream);
+int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                        int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream);
 
 /* ---- ABI v5: live launch timing of one product of the layer executor (diagnostics) ----
  * u2gnn_probe_arm(role, capacity) creates `capacity` pairs of timing events; every following

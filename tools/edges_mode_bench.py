@@ -1,0 +1,152 @@
+"""attention="edges" against "nodes" and "graphs", in one process on the same batches and initial weights:
+
+  * C4: the synthetic batches bench.py times (COLLAB-like, batch_size 64, num_neighbors 16, T 4, ff 1024, fwdh);
+  * a molecule-like setting: MUTAG from dataset/, batch_size 64, the same model shape;
+  * per setting, the fused trainer step (SupTrainer.step, dropout on) under each mode: a warm-up, then blocks of
+    steps in rotating order, every step timed by device events; the median per mode;
+  * the per-launch device time of u2gnn_csr_attn_fwd / _bwd alone at each batch's layer shape (REPS launches
+    captured in one HIP graph), with nnz and sum_g n_g^2 of the batch, against the bytes the gather must move:
+    every entry reads one K and one V row forward (nnz * dp * 4 * 2 B) and K, V, Qs, dO rows backward (twice that),
+    beside the dense QKV / O / dO / dQKV traffic and the entries' indices and (backward) Pd, dS values.
+
+Prints one JSON line.  Usage: python tools/edges_mode_bench.py [--steps 24] [--warmup 5] [--batches 4]"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graph-transformer_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from u2gnn_hip import kernels as K  # noqa: E402
+
+REPS = 20
+MODES = ("nodes", "graphs", "edges")
+
+
+def graph_time_us(fn):
+    """Device microseconds per call: REPS calls captured in one HIP graph, the second replay timed."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        for _ in range(REPS):
+            fn()
+    gr.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    gr.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / REPS
+
+
+def kernel_figures(offsets, adj, d):
+    from u2gnn_hip.engine import row_pad, rup
+    N, dp, nnz = int(offsets[-1]), rup(d, 64), adj.nnz
+    Np = row_pad(N)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    QKV = torch.randn(Np, 3 * dp, device="cuda", generator=g)
+    QKV[:, :dp] *= 1 / math.sqrt(dp)
+    QKV[N:] = 0
+    dO = torch.randn(Np, dp, device="cuda", generator=g)
+    O, stats = torch.empty(Np, dp, device="cuda"), torch.empty(Np, 2, device="cuda")
+    dQKV = torch.empty(Np, 3 * dp, device="cuda")
+    fwd = graph_time_us(lambda: K.csr_attn_fwd(QKV, dp, adj, O, stats, 0.5, 7, N, Np))
+    bwd = graph_time_us(lambda: K.csr_attn_bwd(QKV, dp, adj, O, dO, stats, 0.5, 7, 1 / math.sqrt(d), dQKV, N, Np))
+    sq = float((np.diff(np.asarray(offsets)).astype(np.float64) ** 2).sum())
+    f_gather, b_gather = nnz * dp * 4 * 2, nnz * dp * 4 * 4
+    f_flop, b_flop = 2 * 2 * nnz * dp, 5 * 2 * nnz * dp
+    return {"N": N, "graphs": len(offsets) - 1, "nnz": nnz, "mean_degree": round(nnz / N - 1, 2), "sum_ng2": sq,
+            "fwd_us": round(fwd, 2), "fwd_gather_mb": round(f_gather / 1e6, 2),
+            "fwd_gather_gbs": round(f_gather / fwd / 1e3, 1), "fwd_gflops": round(f_flop / fwd / 1e3, 1),
+            "bwd_us": round(bwd, 2), "bwd_gather_mb": round(b_gather / 1e6, 2),
+            "bwd_gather_gbs": round(b_gather / bwd / 1e3, 1), "bwd_gflops": round(b_flop / bwd / 1e3, 1)}
+
+
+def time_steps(batches, d, C, T, ff, precision, args):
+    from pytorch_U2GNN_Sup import TransformerU2GNN
+    from u2gnn_hip.train import SupTrainer
+    trainers = {}
+    for mode in MODES:
+        torch.manual_seed(123)
+        m = TransformerU2GNN(d, ff, C, T, 0.5, 1, precision=precision, attention=mode).cuda().train()
+        trainers[mode] = SupTrainer(m, lr=5e-4, max_norm=0.5, seed=123)
+    nb = len(batches)
+    for tr in trainers.values():
+        for i in range(args.warmup):
+            tr.step(batches[i % nb])
+    torch.cuda.synchronize()
+    times = {m: [] for m in MODES}
+    done, blk = 0, 0
+    while done < args.steps:
+        order = MODES[blk % 3:] + MODES[:blk % 3]
+        n = min(args.block, args.steps - done)
+        for mode in order:
+            tr = trainers[mode]
+            for i in range(n):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                tr.step(batches[(done + i) % nb])
+                e1.record()
+                torch.cuda.synchronize()
+                times[mode].append(e0.elapsed_time(e1))
+        done += n
+        blk += 1
+    return ({k: round(statistics.median(v), 4) for k, v in times.items()},
+            {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()})
+
+
+def setting(name, store, C, batch_size, k, args):
+    from u2gnn_hip.batching import BatchLoader
+    from u2gnn_hip.core import Adjacency, DeviceBatch
+    T, ff = 4, 1024
+    np.random.seed(123)
+    loader = BatchLoader(store, batch_size, k)
+    host = [loader() for _ in range(args.batches)]
+    batches = []
+    for h in host:
+        b = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
+        b.adj = Adjacency.from_csr(*store.adjacency(h.graph_ids), b.N, device="cuda")
+        batches.append(b)
+    d = host[0].X_concat.shape[1]
+    med, rng = time_steps(batches, d, C, T, ff, args.precision, args)
+    out = {"setting": f"{name}: bs {batch_size}, k {k}, d {d}, T {T}, ff {ff}, {args.precision}, {len(host)} batches, "
+                      f"eager steps, median of {args.steps} per mode in rotating blocks of {args.block}",
+           "step_ms": med, "step_ms_min_max": rng,
+           "edges_over_nodes": round(med["edges"] / med["nodes"], 4),
+           "edges_over_graphs": round(med["edges"] / med["graphs"], 4),
+           "kernels": [kernel_figures(h.offsets, b.adj, d) for h, b in list(zip(host, batches))[:2]]}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=24, help="timed steps per mode (>= 20)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batches", type=int, default=4)
+    ap.add_argument("--block", type=int, default=4, help="steps per rotation block")
+    ap.add_argument("--precision", default="fwdh")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs an MI355X: a timing without one would mean nothing"
+    import util
+    from u2gnn_hip.batching import GraphStore
+    from u2gnn_hip.synthetic import collab_like
+    graphs, C = util.load_data("MUTAG", False)
+    out = {"c4": setting("C4 synthetic", collab_like(seed=0), 3, 64, 16, args),
+           "mutag": setting("MUTAG", GraphStore(graphs), C, 64, 16, args)}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
