@@ -56,9 +56,23 @@ struct Dims {
 // attention over a row pattern (segments or a CSR): the generic route with a statistics-saving fp32 attention kernel
 bool sparse_attn(const Dims &D) { return D.n_seg || D.csr_nnz; }
 
-Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg = nullptr, int n_seg = 0) {
+// The attention pattern of a call (n_seg row segments, a CSR of nnz entries, or neither: the node-axis or window
+// layer).  Segments: offsets and count, both or neither.  CSR: none, or a complete one with at least one entry.  Never
+// the two together, and neither with window mode.  The planning form (u2gnn_layer_sizes_*) has counts only and no
+// pointers.
+bool pattern_ok(const Dims &D, bool plan) {
+    const bool segs = D.seg || D.n_seg, csr = D.csr || D.csr_nnz;
+    if (D.n_seg < 0 || D.csr_nnz < 0 || (segs && csr) || ((segs || csr) && D.window != 0)) return false;
+    if (plan) return true;
+    if (segs && !(D.seg && D.n_seg >= 1)) return false;
+    const u2gnn_csr_attn *A = D.csr;
+    return !csr || (A && A->rowptr && A->colidx && A->t_rowptr && A->t_src && A->t_eid && D.csr_nnz >= 1);
+}
+
+// a: checked by dims_ok; the pattern: to be checked by pattern_ok
+Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg, const u2gnn_csr_attn *csr, int64_t nnz) {
     Dims D;
-    D.seg = seg, D.n_seg = n_seg;
+    D.seg = seg, D.n_seg = n_seg, D.csr = csr, D.csr_nnz = nnz;
     D.N = a->N;
     D.d = a->d;
     D.ff = a->ff;
@@ -128,11 +142,10 @@ bool small_attn(const Dims &D) { return !D.window && !sparse_attn(D) && D.d <= 3
 // (mid_layer.hip; C2: 2 launches instead of 5); engine.mid_tail mirrors the rule
 bool mid_tail(const Dims &D) { return !D.window && !sparse_attn(D) && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
 
-Ctx carve_ctx(Arena &A, const Dims &D, bool drop) {
+Ctx carve_ctx(Arena &A, const Dims &D) {
     Ctx c;
     // the small-width path projects straight into its compact attention context: no [Np][3 dp] image
     c.QKV = small_attn(D) ? nullptr : A.take<float>(D.Np * 3 * D.dp);
-    (void)drop;
     c.Pd = c.Psave = c.stats = nullptr;
     if (D.window)
         c.Psave = A.take<float>(D.N * D.window);
@@ -182,8 +195,12 @@ int32_t h3_prob_exp(float pd) {
     return e;
 }
 
-struct G {   // one GEMM launch (defaults = plain store)
+struct G {   // one GEMM product (defaults = plain store): the launch arguments and what gemm_split reads beside them
     u2gnn_gemm_args a;
+    int probe_role = 0;        // U2GNN_ROLE_*: the launch is bracketed by the probe's events
+    bool accumulate = false;   // gemm_split: C += the product
+    bool deep_k = false;       // gemm_split: weight gradient (16-deep K step, <= 8 slabs)
+    const int64_t *rblk = nullptr, *cblk = nullptr;   // gemm_split: {padded, real} block of C's rows / columns
     G(const float *A, const float *B, float *C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
       int64_t ldc, int prec) {
         std::memset(&a, 0, sizeof(a));
@@ -198,24 +215,35 @@ struct G {   // one GEMM launch (defaults = plain store)
     G &tb() { a.trans_b = 1; return *this; }
     G &epi(int e) { a.epilogue = e; return *this; }
     G &tile(int t) { a.tile = t; return *this; }
-    int run(hipStream_t st, bool plan) { return plan ? U2GNN_OK : u2gnn_gemm(&a, st); }
+    G &alpha(float x) { a.alpha = x; return *this; }
+    G &clamp(bool on) { a.clamp_a = on; return *this; }   // A elements below +0 read as 0 (the signed image as Pd)
+    // f16x3 pre-scale exponent of A when it is not an activation (the probability image: h3_prob_exp)
+    G &h3_a(int32_t e) { if (a.precision == U2GNN_PREC_F16X3) a.h3_exp_a = e; return *this; }
+    G &role(int r) { probe_role = r; return *this; }
+    G &accum() { accumulate = true; return *this; }
+    G &deep() { deep_k = true; return *this; }
+    G &blocks(const int64_t *r, const int64_t *c) { rblk = r, cblk = c; return *this; }
+    int run(hipStream_t st, bool plan) {
+        if (plan) return U2GNN_OK;
+        if (probe_role) probe_mark(probe_role, false, st, plan);
+        const int rc = u2gnn_gemm(&a, st);
+        if (probe_role) probe_mark(probe_role, true, st, plan);
+        return rc;
+    }
 };
-
-hipEvent_t pooled_event();
 
 // Reductions (and weight-gradient products) held back to the end of a latency-bound layer's backward,
 // where they go out as one grouped GEMM launch and one u2gnn_reduce_batch call (<= 2 launches) instead
-// of 12-16 launches of a few microseconds each.  Used when the layer runs on one stream (no side stream:
-// C5, C2, C3).  Every job computes the same bits as its immediate launch (u2gnn_hip.h, ABI v11).
+// of 12-16 launches of a few microseconds each (layer_bwd says which stream each list is flushed on).
+// Every job computes the same bits as its immediate launch (u2gnn_hip.h, ABI v11).
 struct Defer {
     std::vector<u2gnn_reduce_job> red;
     std::vector<u2gnn_gemm_args> gemm;
     std::vector<int> role;   // probe role of each held-back GEMM
-    bool gemms = false;   // hold back the GEMM launches as well (one grouped launch)
+    void hold(const G &g) { gemm.push_back(g.a), role.push_back(g.probe_role); }
 };
 
 int flush(Defer *df, Arena &W, hipStream_t st) {
-    if (!df) return U2GNN_OK;
     const bool plan = W.plan();
     for (size_t o = 0; o < df->gemm.size(); o += 8) {
         const size_t n = std::min<size_t>(8, df->gemm.size() - o);
@@ -247,23 +275,37 @@ u2gnn_reduce_job rjob(int kind) {
     return j;
 }
 
+struct Slabs {   // split-K partial sums left to their consumer (p null: the product was completed)
+    float *p = nullptr;
+    int64_t n = 0;
+};
+struct To {   // where a gemm_split product goes (defaults = launched and completed on st)
+    hipStream_t st;
+    Defer *held = nullptr;    // non-null: the launch and its slab reduce join this list's flush instead
+    Slabs *slabs = nullptr;   // non-null: a split product leaves its slabs here instead of reducing them
+    explicit To(hipStream_t s) : st(s) {}
+    To &hold(Defer *df) { held = df; return *this; }
+    To &leave_slabs(Slabs *s) { slabs = s; return *this; }
+};
+
 // split-K block targets (engine._gemm_split): 448 blocks for 64 / 128 tiles, 240 for 256x128 tiles
 // (round-2 sweeps: 224 / 896 within noise, 120 / 300 / 460 slower on the 256x128 products)
 constexpr int64_t kSplitTarget = 448, kSplitTarget256 = 240;
 
 // engine._gemm_split: deterministic split-K into fp32 slabs + one reduce pass (alpha, accumulate,
-// padded->real block map).  deep = weight gradient (16-deep K step, <= 8 slabs).  red_st: run the
-// reduce pass on that stream after the GEMM (pooled fork event; the caller joins it back).
-int gemm_split(Arena &W, const Dims &D, const float *A, const float *B, float *C, int64_t M, int64_t N, int64_t Kd,
-               int64_t lda, int64_t ldb, int64_t ldc, bool ta, float alpha, bool accumulate, const int64_t *rblk,
-               const int64_t *cblk, bool deep, hipStream_t st, bool clamp_a = false, int prec = -1, int role = 0,
-               hipStream_t red_st = nullptr, Defer *df = nullptr, float **slabs_out = nullptr,
-               int64_t *nslab_out = nullptr, int32_t h3_exp_a = kH3Exp) {
-    if (prec < 0) prec = D.prec;
-    const bool f32 = prec == U2GNN_PREC_F32;
+// padded->real block map).  g describes the finished product (its C, ldc, alpha and accumulate are the
+// result's; deep = weight gradient: 16-deep K step, <= 8 slabs), `to` where it goes.
+int gemm_split(Arena &W, const Dims &D, G g, const To &to) {
+    const int64_t M = g.a.M, N = g.a.N, Kd = g.a.K;
+    const int role = g.probe_role;
+    const bool accumulate = g.accumulate, deep = g.deep_k;
+    hipStream_t st = to.st;
+    Defer *df = to.held;
+    const bool f32 = g.a.precision == U2GNN_PREC_F32;
     const int64_t bk = f32 ? 16 : 32;
     const bool plan = W.plan();
-    const bool mapped = rblk != nullptr;
+    const bool mapped = g.rblk != nullptr;
+    g.epi(accumulate ? U2GNN_EPI_ACCUM : U2GNN_EPI_STORE);   // (the slab exit stores; its reduce accumulates)
     // (tiny: an accumulating product of at most 16 tiles and 16 K steps -- C2's dX += dQKV W_in, 4 tiles --
     // runs as one short launch instead of 3 split-K blocks + a reduce launch; engine._gemm_split mirrors it)
     const bool tiny = accumulate && Kd <= 512 && (M / 64) * (N / 64) <= 16;
@@ -271,17 +313,8 @@ int gemm_split(Arena &W, const Dims &D, const float *A, const float *B, float *C
         ((M / 64) * (N / 64) >= 256 || tiny)) {
         // shallow K (dH.W1, dQKV.W_in) with enough 64x64 tiles to fill the chip: no split, the
         // epilogue accumulates straight into C (no slabs, no reduce pass)
-        G g(A, B, C, M, N, Kd, lda, ldb, ldc, prec);
-        if (ta) g.ta();
-        g.a.alpha = alpha;
-        g.a.clamp_a = clamp_a;
-        if (prec == U2GNN_PREC_F16X3) g.a.h3_exp_a = h3_exp_a;
         const bool big = M % 256 == 0 && N % 128 == 0 && (M / 256) * (N / 128) >= U2GNN_BIG_TILE_BLOCKS;
-        g.epi(accumulate ? U2GNN_EPI_ACCUM : U2GNN_EPI_STORE).tile(big ? 256 : 64);
-        probe_mark(role, false, st, plan);
-        const int rc = g.run(st, plan);
-        probe_mark(role, true, st, plan);
-        return rc;
+        return g.tile(big ? 256 : 64).run(st, plan);
     }
     int t;
     int64_t tiles, target = kSplitTarget;
@@ -313,91 +346,53 @@ int gemm_split(Arena &W, const Dims &D, const float *A, const float *B, float *C
     // A launch of fewer than 64 blocks of 128x128 runs them as 64x64 tiles too (4x the blocks for the same
     // sums; C2's dX1 = dH W1: 8 blocks of a 4-step K loop, 8.6 us)
     // (bf16 precisions, whose 64x64 and 128x128 kernels form the same k-ordered sums)
-    const int t_group = (!f32 && t == 128 && ((df && df->gemms) || (M / 128) * (N / 128) * split < 64)) ? 64 : t;
+    const int t_group = (!f32 && t == 128 && (df || (M / 128) * (N / 128) * split < 64)) ? 64 : t;
+    g.tile(t_group);
     if (split == 1 && !mapped) {
-        G g(A, B, C, M, N, Kd, lda, ldb, ldc, prec);
-        if (ta) g.ta();
-        g.a.alpha = alpha;
-        g.a.clamp_a = clamp_a;
-        if (prec == U2GNN_PREC_F16X3) g.a.h3_exp_a = h3_exp_a;
-        g.epi(accumulate ? U2GNN_EPI_ACCUM : U2GNN_EPI_STORE).tile(t_group);
-        if (df && df->gemms && !accumulate) {
-            df->gemm.push_back(g.a);
-            df->role.push_back(role);
+        if (df && !accumulate) {
+            df->hold(g);
             return U2GNN_OK;
         }
-        probe_mark(role, false, st, plan);
-        const int rc = g.run(st, plan);
-        probe_mark(role, true, st, plan);
-        return rc;
+        return g.run(st, plan);
     }
+    // split-K: the GEMM stores plain partial sums into slabs; alpha, accumulate and the block map are the reduce's
     float *slabs = W.take<float>(split * M * N);
-    G g(A, B, slabs, M, N, Kd, lda, ldb, N, prec);
-    if (ta) g.ta();
-    g.a.split_k = (int32_t)split;
-    g.a.slab_stride = M * N;
-    g.a.clamp_a = clamp_a;
-    if (prec == U2GNN_PREC_F16X3) g.a.h3_exp_a = h3_exp_a;
-    g.tile(t_group);
-    const int64_t rb0 = rblk ? rblk[0] : M, rb1 = rblk ? rblk[1] : M;
-    const int64_t cb0 = cblk ? cblk[0] : N, cb1 = cblk ? cblk[1] : N;
-    if (df) {   // slab reduce (and with df->gemms the GEMM itself) at the layer's flush
-        if (df->gemms) {
-            df->gemm.push_back(g.a);
-            df->role.push_back(role);
-        } else {
-            probe_mark(role, false, st, plan);
-            U2GNN_TRY(g.run(st, plan));
-            probe_mark(role, true, st, plan);
-        }
-        u2gnn_reduce_job j = rjob(U2GNN_RJOB_SLAB);
-        j.src = slabs, j.n_slab = (int32_t)split, j.slab_stride = M * N, j.rows = M, j.cols = N, j.ld_src = N;
-        j.rblk_pad = rb0, j.rblk_real = rb1, j.cblk_pad = cb0, j.cblk_real = cb1;
-        j.dst = C, j.ld_dst = ldc, j.alpha = alpha, j.accumulate = accumulate ? 1 : 0;
+    u2gnn_reduce_job j = rjob(U2GNN_RJOB_SLAB);
+    j.src = slabs, j.n_slab = (int32_t)split, j.slab_stride = M * N, j.rows = M, j.cols = N, j.ld_src = N;
+    j.rblk_pad = g.rblk ? g.rblk[0] : M, j.rblk_real = g.rblk ? g.rblk[1] : M;
+    j.cblk_pad = g.cblk ? g.cblk[0] : N, j.cblk_real = g.cblk ? g.cblk[1] : N;
+    j.dst = g.a.C, j.ld_dst = g.a.ldc, j.alpha = g.a.alpha, j.accumulate = accumulate ? 1 : 0;
+    g.a.C = slabs, g.a.ldc = N, g.a.split_k = (int32_t)split, g.a.slab_stride = M * N;
+    g.epi(U2GNN_EPI_STORE).alpha(1.f);
+    if (df) {   // the GEMM and its slab reduce at the layer's flush
+        df->hold(g);
         df->red.push_back(j);
         return U2GNN_OK;
     }
-    probe_mark(role, false, st, plan);
     U2GNN_TRY(g.run(st, plan));
-    probe_mark(role, true, st, plan);
-    if (slabs_out) {   // the consumer sums the slabs itself (u2gnn_layernorm_bwd_delta_slabs)
-        *slabs_out = slabs, *nslab_out = split;
+    if (to.slabs) {   // the consumer sums the slabs itself (u2gnn_layernorm_bwd_delta_slabs)
+        to.slabs->p = slabs, to.slabs->n = split;
         return U2GNN_OK;
     }
     if (plan) return U2GNN_OK;
-    hipStream_t rs = st;
-    if (red_st && red_st != st) {
-        hipEvent_t ev = pooled_event();
-        if (!ev) return U2GNN_E_ARG;
-        if (hipEventRecord(ev, st) != hipSuccess || hipStreamWaitEvent(red_st, ev, 0) != hipSuccess) return U2GNN_E_ARG;
-        rs = red_st;
-    }
-    return u2gnn_slab_reduce(slabs, (int32_t)split, M * N, M, N, N, rb0, rb1, cb0, cb1, C, ldc, alpha,
-                             accumulate ? 1 : 0, rs);
+    return u2gnn_slab_reduce(slabs, j.n_slab, j.slab_stride, M, N, N, j.rblk_pad, j.rblk_real, j.cblk_pad, j.cblk_real,
+                             j.dst, j.ld_dst, j.alpha, j.accumulate, st);
 }
 
-// engine._wgrad: dst(real) = unpack(dY^T X)
+// engine._wgrad: dst(real) = unpack(dY^T X), held back to df's flush
 int wgrad(Arena &W, const Dims &D, const float *dY, int64_t ld_dy, const float *X, int64_t ld_x, int64_t m_pad,
           int64_t n_pad, float *dst, int64_t ld_dst, const int64_t *rblk, const int64_t *cblk, hipStream_t st,
-          Defer *df = nullptr) {
-    return gemm_split(W, D, dY, X, dst, m_pad, n_pad, D.Np, ld_dy, ld_x, ld_dst, true, 1.f, false, rblk, cblk, true,
-                      st, false, -1, 0, nullptr, df);
+          Defer *df) {
+    G g(dY, X, dst, m_pad, n_pad, D.Np, ld_dy, ld_x, ld_dst, D.prec);
+    return gemm_split(W, D, g.ta().blocks(rblk, cblk).deep(), To(st).hold(df));
 }
 
-int64_t colstat_ws_floats(int64_t rows, int64_t cols) { return ((rows + 15) / 16 > 0 ? (rows + 15) / 16 : 1) * 3 * cols; }
-
-int bias_grad(Arena &W, const float *dY, int64_t rows, int64_t cols_pad, int64_t ld, int64_t cb0, int64_t cb1,
-              float *out, hipStream_t st, Defer *df = nullptr) {
-    // taken in both modes: the size plan (u2gnn_layer_sizes runs the one-stream form) covers the side-stream form
-    float *ws = W.take<float>(colstat_ws_floats(rows, cols_pad));
-    if (df) {
-        u2gnn_reduce_job j = rjob(U2GNN_RJOB_COLSUM);
-        j.src = dY, j.rows = rows, j.cols = cols_pad, j.ld_src = ld, j.cblk_pad = cb0, j.cblk_real = cb1, j.dst = out;
-        df->red.push_back(j);
-        return U2GNN_OK;
-    }
-    if (W.plan()) return U2GNN_OK;
-    return u2gnn_colsum(dY, rows, cols_pad, ld, cb0, cb1, out, 0, ws, st);
+// a column sum of dY as a job of the layer's flush
+void bias_grad(Defer *df, const float *dY, int64_t rows, int64_t cols_pad, int64_t ld, int64_t cb0, int64_t cb1,
+               float *out) {
+    u2gnn_reduce_job j = rjob(U2GNN_RJOB_COLSUM);
+    j.src = dY, j.rows = rows, j.cols = cols_pad, j.ld_src = ld, j.cblk_pad = cb0, j.cblk_real = cb1, j.dst = out;
+    df->red.push_back(j);
 }
 
 // Fork / join events come from a per-device ring of pre-created events.  Re-recording an event is
@@ -446,12 +441,6 @@ struct Side {
         if (e == hipSuccess) e = hipStreamWaitEvent(side, ev, 0);
         return e == hipSuccess ? U2GNN_OK : (int)e;
     }
-    // the main stream waits for everything issued on the side stream so far
-    int join() {
-        hipEvent_t ev = nullptr;
-        U2GNN_TRY(mark(&ev));
-        return wait(ev);
-    }
     // an event at the side stream's current position (joined later by wait(); nullptr when there
     // is no separate side stream)
     int mark(hipEvent_t *ev) {
@@ -470,19 +459,13 @@ struct Side {
     }
 };
 
-// u2gnn_layernorm_bwd_params now, or as a job of the layer's flush
-int ln_params(const float *dY, const float *Z, const float *mean, const float *rstd, const float *dZd, int64_t ld,
-              int64_t rows, int64_t d, int64_t dp, float *ws, float *dgamma, float *dbeta, float *dbias, hipStream_t st,
-              bool plan, Defer *df) {
-    if (df) {
-        u2gnn_reduce_job j = rjob(U2GNN_RJOB_LNPARAMS);
-        j.src = dY, j.ld_src = ld, j.Z = Z, j.ldz = ld, j.mean = mean, j.rstd = rstd, j.dZdrop = dZd, j.lddrop = ld;
-        j.rows = rows, j.d = d, j.cols = dp, j.dst = dgamma, j.dbeta = dbeta, j.dbias = dbias;
-        df->red.push_back(j);
-        return U2GNN_OK;
-    }
-    if (plan) return U2GNN_OK;
-    return u2gnn_layernorm_bwd_params(dY, ld, Z, ld, mean, rstd, dZd, ld, rows, d, dp, ws, dgamma, dbeta, dbias, st);
+// u2gnn_layernorm_bwd_params as a job of the layer's flush
+void ln_params(Defer *df, const float *dY, const float *Z, const float *mean, const float *rstd, const float *dZd,
+               int64_t ld, int64_t rows, int64_t d, int64_t dp, float *dgamma, float *dbeta, float *dbias) {
+    u2gnn_reduce_job j = rjob(U2GNN_RJOB_LNPARAMS);
+    j.src = dY, j.ld_src = ld, j.Z = Z, j.ldz = ld, j.mean = mean, j.rstd = rstd, j.dZdrop = dZd, j.lddrop = ld;
+    j.rows = rows, j.d = d, j.cols = dp, j.dst = dgamma, j.dbeta = dbeta, j.dbias = dbias;
+    df->red.push_back(j);
 }
 
 // Schedule decisions (each measured in rounds 1-2; the A/B switches are gone):
@@ -525,13 +508,7 @@ int qk_tile(int64_t Np) { return (Np % 256 == 0 && (Np / 256) * (Np / 128) >= 25
 // three-pass (r6h) vs 0.460 fused (r6i); engine.FUSED_MIN_NP mirrors the bound
 constexpr int64_t kFusedMinNp = 1024;
 bool fused_attn(const Dims &D) {
-#ifdef U2GNN_EXP_H3_UNFUSED   // (A/B: the fwdh policy on the three-pass forward)
-    if (D.prec_fwd == U2GNN_PREC_F16X3) return false;
-#endif
-#ifndef U2GNN_EXP_FUSED_ANY_NP   // (A/B: the fused form at every row count, as up to r6i)
-    if (D.Np < kFusedMinNp) return false;
-#endif
-    return !D.window && !sparse_attn(D) && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 &&
+    return D.Np >= kFusedMinNp && !D.window && !sparse_attn(D) && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 &&
            D.prec_fwd != U2GNN_PREC_BF16X6 && D.dp <= 384;
 }
 
@@ -559,7 +536,7 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     const float pd = s->p_drop;
     const bool drop = pd > 0.f;
     const bool plan = W.plan();
-    Ctx c = carve_ctx(need_ctx ? CA : W, D, drop);
+    Ctx c = carve_ctx(need_ctx ? CA : W, D);
     const bool fused = fused_attn(D);
     // the in-projection output again in x2 format: the V tiles the fused softmax.P.V kernel reads (bf16x6: it reads
     // the fp32 output itself and splits V in registers, no copy)
@@ -571,11 +548,8 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         // 256x128 blocks from 3 waves of them on (token-sized rows, neighbour mode), the default tile
         // rule below that: C4's 19 x 9 blocks of 256x128 leave a third of the CUs idle, its 76 x 18 64-tile
         // blocks run the step 0.8 % faster (3/3 reps, profiles/r02/qkv_tile_ab.txt; bit-identical).
-        int qkv_tile = (prec != U2GNN_PREC_F32 && Np % 256 == 0 &&
-                        (Np / 256) * (3 * dp / 128) >= U2GNN_BIG_TILE_BLOCKS) ? 256 : 0;
-#ifdef U2GNN_EXP_QKV256   // (A/B: 256x128 blocks for every in-projection with Np % 256 == 0)
-        if (prec != U2GNN_PREC_F32 && Np % 256 == 0) qkv_tile = 256;
-#endif
+        const int qkv_tile = (prec != U2GNN_PREC_F32 && Np % 256 == 0 &&
+                              (Np / 256) * (3 * dp / 128) >= U2GNN_BIG_TILE_BLOCKS) ? 256 : 0;
         g.tb().epi(U2GNN_EPI_BIAS).tile(qkv_tile);
         g.a.bias = w->b_in;
         g.a.alpha = (float)(1.0 / std::sqrt((double)d));
@@ -618,11 +592,9 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         float *pv_ws = W.take<float>(u2gnn_attn_softmax_pv_ws_floats(N, Np, dp));
         {
             G g(Q, Kt, c.Pd, Np, Np, dp, 3 * dp, 3 * dp, Np, prec);
-            g.tb().epi(U2GNN_EPI_STORE_ROWSTAT).tile(qk_tile(Np));
+            g.tb().epi(U2GNN_EPI_STORE_ROWSTAT).tile(qk_tile(Np)).role(U2GNN_ROLE_QK);
             g.a.rowpart = rowpart, g.a.ld_rowpart = ld_rp, g.a.n_valid = N;
-            probe_mark(U2GNN_ROLE_QK, false, st, plan);
             U2GNN_TRY(g.run(st, plan));
-            probe_mark(U2GNN_ROLE_QK, true, st, plan);
         }
         if (!plan) {
             probe_mark(U2GNN_ROLE_PV, false, st, plan);
@@ -636,17 +608,14 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         float *S = W.take<float>(Np * Np);
         {
             G g(Q, Kt, S, Np, Np, dp, 3 * dp, 3 * dp, Np, prec);
-            g.tb().tile((prec != U2GNN_PREC_F32 && Np % 256 == 0) ? 256 : 0);
-            probe_mark(U2GNN_ROLE_QK, false, st, plan);
+            g.tb().tile((prec != U2GNN_PREC_F32 && Np % 256 == 0) ? 256 : 0).role(U2GNN_ROLE_QK);
             U2GNN_TRY(g.run(st, plan));
-            probe_mark(U2GNN_ROLE_QK, true, st, plan);
         }
         if (!plan)
             U2GNN_TRY(u2gnn_attn_softmax_fwd(S, Np, drop ? nullptr : c.Pd, c.Pd, Np, N, Np, N, Np, pd, s->attn,
                                              nullptr, 0, st));
-        U2GNN_TRY(gemm_split(W, D, c.Pd, V, c.O, Np, dp, Np, Np, 3 * dp, dp, false, 1.f, false, nullptr, nullptr,
-                             false, st, drop, prec, U2GNN_ROLE_PV, nullptr, nullptr, nullptr, nullptr,
-                             h3_prob_exp(pd)));
+        U2GNN_TRY(gemm_split(W, D, G(c.Pd, V, c.O, Np, dp, Np, Np, 3 * dp, dp, prec).clamp(drop).h3_a(h3_prob_exp(pd))
+                                       .role(U2GNN_ROLE_PV), To(st)));
     }
     if (small_attn(D)) {
         // a3.3 + a3.4: run by u2gnn_layer_small_fwd above
@@ -676,9 +645,6 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         {
             G g(c.X1, w->W1, c.Hd, Np, ffp, dp, dp, dp, ffp, prec);
             g.tb().epi(U2GNN_EPI_BIAS_RELU_DROP);
-#ifdef U2GNN_EXP_FFN1_256   // (A/B: FFN1 on 256x128 blocks)
-            if (prec != U2GNN_PREC_F32 && Np % 256 == 0 && ffp % 128 == 0) g.tile(256);
-#endif
             g.a.bias = w->b1, g.a.p_drop = pd, g.a.seed = s->dropff;
             U2GNN_TRY(g.run(st, plan));
         }
@@ -717,9 +683,8 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     const int64_t N = D.N, Np = D.Np, d = D.d, dp = D.dp, ff = D.ff, ffp = D.ffp;
     const int prec = D.prec;
     const float pd = s->p_drop;
-    const bool drop = pd > 0.f;
     const bool plan = W.plan();
-    Ctx c = carve_ctx(CA, D, drop);
+    Ctx c = carve_ctx(CA, D);
     Side sd{st, side_st ? side_st : st, plan};
     hipStream_t so = sd.side;
     // The parameter-gradient products and reductions are held back to the end of the layer (df) and go out
@@ -730,10 +695,8 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     // dQ, dK (and dV when it runs on this stream) go out as one grouped launch and their slab reduces as
     // one batch before the in-projection (att; C4 neutral, C5 -2 launches per layer).
     Defer defer_p, defer_a;
-    defer_p.gemms = defer_a.gemms = true;
     Defer *df = &defer_p, *att = &defer_a;
     const int64_t blk_d[2] = {dp, d}, blk_ff[2] = {ffp, ff};
-    float *ws = W.take<float>(colstat_ws_floats(N, dp));
     const bool tail = small_attn(D);   // the row-local tail kernel (small_layer.hip) forms dX1 ... dO and delta
     // one-stream layers in the matrix-core precisions: LayerNorm1's backward forms delta = rowsum(dO * O)
     const bool ln_delta = !D.window && !sparse_attn(D) && prec != U2GNN_PREC_F32;
@@ -762,18 +725,18 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
             probe_mark(U2GNN_ROLE_DS, true, st, plan);
         }
         // the parameter gradients of the tail, held back (df) in the order of the matrix-core branch
-        U2GNN_TRY(ln_params(dX2, c.Z2, c.mean2, c.rstd2, dF, dp, N, d, dp, ws, g->n2_w, g->n2_b, g->l2_b, so, plan, df));
+        ln_params(df, dX2, c.Z2, c.mean2, c.rstd2, dF, dp, N, d, dp, g->n2_w, g->n2_b, g->l2_b);
         U2GNN_TRY(wgrad(W, D, dF, dp, c.Hd, ffp, dp, ffp, g->l2_w, ff, blk_d, blk_ff, so, df));
         U2GNN_TRY(wgrad(W, D, dH, ffp, c.X1, dp, ffp, dp, g->l1_w, d, blk_ff, blk_d, so, df));
-        U2GNN_TRY(bias_grad(W, dH, Np, ffp, ffp, ffp, ff, g->l1_b, so, df));
-        U2GNN_TRY(ln_params(dX1, c.Z1, c.mean1, c.rstd1, dA, dp, N, d, dp, ws, g->n1_w, g->n1_b, g->out_b, so, plan, df));
+        bias_grad(df, dH, Np, ffp, ffp, ffp, ff, g->l1_b);
+        ln_params(df, dX1, c.Z1, c.mean1, c.rstd1, dA, dp, N, d, dp, g->n1_w, g->n1_b, g->out_b);
         U2GNN_TRY(wgrad(W, D, dA, dp, c.O, dp, dp, dp, g->out_w, d, blk_d, blk_d, so, df));
     } else {
         // LN2 backward -> dX1 (residual), dF (dropout2 branch); norm2 + linear2.bias grads (held back: df)
         if (!plan)
             U2GNN_TRY(u2gnn_layernorm_bwd(dX2, dp, c.Z2, dp, c.mean2, c.rstd2, w->n2_w, dX1, dp, dF, dp, pd, s->drop2,
                                           N, Np, d, dp, st));
-        U2GNN_TRY(ln_params(dX2, c.Z2, c.mean2, c.rstd2, dF, dp, N, d, dp, ws, g->n2_w, g->n2_b, g->l2_b, so, plan, df));
+        ln_params(df, dX2, c.Z2, c.mean2, c.rstd2, dF, dp, N, d, dp, g->n2_w, g->n2_b, g->l2_b);
         // FFN
         {
             G gg(dF, w->W2, dH, Np, ffp, dp, dp, ffp, ffp, prec);
@@ -784,17 +747,15 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         U2GNN_TRY(wgrad(W, D, dF, dp, c.Hd, ffp, dp, ffp, g->l2_w, ff, blk_d, blk_ff, so, df));   // held back (df)
         // one-stream layers in the matrix-core precisions: a split-K dX1 product leaves its slabs to LayerNorm1's
         // backward, which completes dX1 before using it (the separate reduce launch goes; same bits)
-        float *dx1_slabs = nullptr;
-        int64_t dx1_nslab = 0;
-        U2GNN_TRY(gemm_split(W, D, dH, w->W1, dX1, Np, dp, ffp, ffp, dp, dp, false, 1.f, true, nullptr, nullptr, false,
-                             st, false, -1, 0, nullptr, nullptr, (ln_delta && so == st) ? &dx1_slabs : nullptr,
-                             &dx1_nslab));
+        Slabs dx1_slabs;
+        U2GNN_TRY(gemm_split(W, D, G(dH, w->W1, dX1, Np, dp, ffp, ffp, dp, dp, prec).accum(),
+                             To(st).leave_slabs((ln_delta && so == st) ? &dx1_slabs : nullptr)));
         U2GNN_TRY(wgrad(W, D, dH, ffp, c.X1, dp, ffp, dp, g->l1_w, d, blk_ff, blk_d, so, df));
-        U2GNN_TRY(bias_grad(W, dH, Np, ffp, ffp, ffp, ff, g->l1_b, so, df));
+        bias_grad(df, dH, Np, ffp, ffp, ffp, ff, g->l1_b);
         // LN1 backward -> dX (residual), dA (dropout1 branch); norm1 + out_proj.bias grads (held back: df);
         // node attention: LayerNorm1's backward also forms delta = rowsum(dO * O) for the dS epilogue
-        if (!plan && ln_delta && dx1_slabs)
-            U2GNN_TRY(u2gnn_layernorm_bwd_delta_slabs(dX1, dp, dx1_slabs, (int32_t)dx1_nslab, Np * dp, c.Z1, dp,
+        if (!plan && ln_delta && dx1_slabs.p)
+            U2GNN_TRY(u2gnn_layernorm_bwd_delta_slabs(dX1, dp, dx1_slabs.p, (int32_t)dx1_slabs.n, Np * dp, c.Z1, dp,
                                                       c.mean1, c.rstd1, w->n1_w, dX, dp, dA, dp, pd, s->drop1, N, Np, d,
                                                       dp, X, dp, w->b_o, delta_ln, st));
         else if (!plan && ln_delta)
@@ -803,8 +764,7 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         else if (!plan)
             U2GNN_TRY(u2gnn_layernorm_bwd(dX1, dp, c.Z1, dp, c.mean1, c.rstd1, w->n1_w, dX, dp, dA, dp, pd, s->drop1,
                                           N, Np, d, dp, st));
-        U2GNN_TRY(ln_params(dX1, c.Z1, c.mean1, c.rstd1, dA, dp, N, d, dp, ws, g->n1_w, g->n1_b, g->out_b, so, plan,
-                            df));
+        ln_params(df, dX1, c.Z1, c.mean1, c.rstd1, dA, dp, N, d, dp, g->n1_w, g->n1_b, g->out_b);
         // out-projection
         {
             G gg(dA, w->W_o, dO, Np, dp, dp, dp, dp, dp, prec);
@@ -846,46 +806,38 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         const bool dv_side = so != st;   // grouped with dQ / dK on this stream instead: 3.136-3.141 vs 3.068-3.098 ms
         // dV needs only Pd and dO: on the side stream it overlaps the dS -> dQ -> dK chain
         U2GNN_TRY(sd.fork());
-        U2GNN_TRY(gemm_split(W, D, c.Pd, dO, dQKV + 2 * dp, Np, dp, Np, Np, dp, 3 * dp, true, 1.f, false, nullptr,
-                             nullptr, false, dv_side ? so : st, pd > 0.f, -1, U2GNN_ROLE_DV, nullptr,
-                             dv_side ? nullptr : att));
+        U2GNN_TRY(gemm_split(W, D, G(c.Pd, dO, dQKV + 2 * dp, Np, dp, Np, Np, dp, 3 * dp, prec).ta().clamp(pd > 0.f)
+                                       .role(U2GNN_ROLE_DV), To(dv_side ? so : st).hold(dv_side ? nullptr : att)));
         if (dv_side) U2GNN_TRY(sd.mark(&dv_done));
-#ifdef U2GNN_EXP_EARLY_FLUSH
-        // experiment: the layer's held-back FFN / LayerNorm / out-projection parameter work goes out on the
-        // side stream behind dV (beside dS, dQ, dK) instead of at the end of the layer (beside the next
-        // layer's FFN backward); only the in-projection's gradients are left for the end
-        if (dv_side && need_dx) U2GNN_TRY(flush(df, W, so));   // measured neutral-to-worse (r04 A/B)
-#endif
+        // (the layer's held-back parameter work flushed here, on the side stream behind dV, instead of at the end of
+        // the layer: measured neutral-to-worse, C4 3.067 / 3.088 ms per step)
         float *delta = have_delta ? delta_ln : W.take<float>(Np);
         if (!plan && !have_delta) U2GNN_TRY(u2gnn_rowdot(dO, dp, c.O, dp, delta, Np, dp, st));
         float *dS = W.take<float>(Np * Np);
         {
             G gg(dO, V, dS, Np, Np, dp, dp, 3 * dp, Np, D.prec_ab);
-            gg.tb().epi(U2GNN_EPI_ATTN_DS_SIGNED);
+            gg.tb().epi(U2GNN_EPI_ATTN_DS_SIGNED).role(U2GNN_ROLE_DS);
             gg.a.aux0 = c.Pd, gg.a.rowvec = delta, gg.a.ld_aux = Np, gg.a.p_drop = pd;
-            probe_mark(U2GNN_ROLE_DS, false, st, plan);
             U2GNN_TRY(gg.run(st, plan));
-            probe_mark(U2GNN_ROLE_DS, true, st, plan);
         }
-        U2GNN_TRY(gemm_split(W, D, dS, Kt, dQKV, Np, dp, Np, Np, 3 * dp, 3 * dp, false, q_scale, false, nullptr, nullptr,
-                             false, st, false, D.prec_ab, U2GNN_ROLE_DQ, nullptr, att));
-        U2GNN_TRY(gemm_split(W, D, dS, Q, dQKV + dp, Np, dp, Np, Np, 3 * dp, 3 * dp, true, 1.f, false, nullptr,
-                             nullptr, false, st, false, D.prec_ab, U2GNN_ROLE_DK, nullptr, att));
+        U2GNN_TRY(gemm_split(W, D, G(dS, Kt, dQKV, Np, dp, Np, Np, 3 * dp, 3 * dp, D.prec_ab).alpha(q_scale)
+                                       .role(U2GNN_ROLE_DQ), To(st).hold(att)));
+        U2GNN_TRY(gemm_split(W, D, G(dS, Q, dQKV + dp, Np, dp, Np, Np, 3 * dp, 3 * dp, D.prec_ab).ta()
+                                       .role(U2GNN_ROLE_DK), To(st).hold(att)));
         U2GNN_TRY(flush(att, W, st));
         U2GNN_TRY(sd.wait(dv_done));   // dV before dX += dQKV W_in
     }
     // in-projection
     if (need_dx && !small_attn(D))
-        U2GNN_TRY(gemm_split(W, D, dQKV, w->W_in, dX, Np, dp, 3 * dp, 3 * dp, dp, dp, false, 1.f, true, nullptr,
-                             nullptr, false, st));
+        U2GNN_TRY(gemm_split(W, D, G(dQKV, w->W_in, dX, Np, dp, 3 * dp, 3 * dp, dp, dp, prec).accum(), To(st)));
     U2GNN_TRY(wgrad(W, D, dQKV, 3 * dp, X, dp, 3 * dp, dp, g->in_w, d, blk_d, blk_d, st, df));
     // in_proj_bias: the Q and V thirds are column sums of dQKV; the K third is exactly zero -- a softmax row is
     // invariant to a constant added to its scores, so sum_j dK_j = sum_i Q_i sum_j dS_ij = 0.  The reference's
     // value there is summation noise, which Adam's first step (lr g / (|g| + eps)) turns into moves of up to lr;
     // a column sum over zero rows writes the exact zeros (engine.in_bias_grad mirrors this)
-    U2GNN_TRY(bias_grad(W, dQKV, Np, dp, 3 * dp, dp, d, g->in_b, st, df));
-    U2GNN_TRY(bias_grad(W, dQKV + dp, 0, dp, 3 * dp, dp, d, g->in_b + d, st, df));
-    U2GNN_TRY(bias_grad(W, dQKV + 2 * dp, Np, dp, 3 * dp, dp, d, g->in_b + 2 * d, st, df));
+    bias_grad(df, dQKV, Np, dp, 3 * dp, dp, d, g->in_b);
+    bias_grad(df, dQKV + dp, 0, dp, 3 * dp, dp, d, g->in_b + d);
+    bias_grad(df, dQKV + 2 * dp, Np, dp, 3 * dp, dp, d, g->in_b + 2 * d);
     // the held-back work: on the side stream after everything issued so far, except for the last layer of
     // the backward (need_dx false), where nothing is left to overlap and the hand-off plus the step's final
     // join cost more than the products (C4 round 3: 3.140-3.157 vs 3.171-3.194 ms per step)
@@ -904,22 +856,17 @@ bool dims_ok(const u2gnn_layer_dims *a) {
            a->window >= 0 && a->window <= 32 && (a->window == 0 || a->N % a->window == 0);
 }
 
-// per-graph attention arguments: both or neither (neither = the node-axis layer), never with window mode
-bool seg_ok(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg) {
-    if (!seg && n_seg == 0) return true;
-    return seg && n_seg >= 1 && a->window == 0;
-}
-
-// neighbour attention argument: none, or a complete CSR; never with window mode or with segments
-bool csr_ok(const u2gnn_layer_dims *a, int32_t n_seg, const u2gnn_csr_attn *A) {
-    if (!A) return true;
-    return A->rowptr && A->colidx && A->t_rowptr && A->t_src && A->t_eid && A->nnz >= 1 && a->window == 0 && n_seg == 0;
-}
-
-Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int n_seg, const u2gnn_csr_attn *A) {
-    Dims D = make_dims(a, seg, n_seg);
-    if (A) D.csr = A, D.csr_nnz = A->nnz;
-    return D;
+// Plan, then run: the same call in planning mode first (run(ctx arena, workspace arena) is the layer call), so a
+// workspace or ctx arena smaller than this call takes is refused before anything is launched (never a launch over
+// the end of a caller buffer).  ctx null: the call saves nothing (forward without a backward).
+template <typename Run>
+int plan_then_run(void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes, Run run) {
+    Arena Pc(nullptr, 0), Pw(nullptr, 0);
+    run(Pc, Pw);
+    if (Pw.used > (ws ? ws_bytes : 0) || (ctx && Pc.used > ctx_bytes)) return U2GNN_E_ARG;
+    static char empty_ws alignas(256)[256];   // a null base would mean "plan only"
+    Arena C(ctx, ctx_bytes), W(ws ? ws : empty_ws, ws ? ws_bytes : 0);
+    return run(C, W);
 }
 
 }  // namespace
@@ -929,10 +876,8 @@ extern "C" {
 int u2gnn_layer_sizes_csr(const u2gnn_layer_dims *dims, float p_drop, int32_t n_seg, int64_t nnz, int64_t *ctx_bytes,
                           int64_t *fwd_ws_bytes, int64_t *bwd_ws_bytes) {
     if (!dims_ok(dims) || !ctx_bytes || !fwd_ws_bytes || !bwd_ws_bytes) return U2GNN_E_ARG;
-    if (n_seg < 0 || (n_seg && dims->window)) return U2GNN_E_ARG;
-    if (nnz < 0 || (nnz && (dims->window || n_seg))) return U2GNN_E_ARG;
-    Dims D = make_dims(dims, nullptr, n_seg);
-    D.csr_nnz = nnz;
+    const Dims D = make_dims(dims, nullptr, n_seg, nullptr, nnz);
+    if (!pattern_ok(D, true)) return U2GNN_E_ARG;
     u2gnn_layer_seeds s;
     std::memset(&s, 0, sizeof(s));
     s.p_drop = p_drop;
@@ -963,16 +908,11 @@ int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
                         const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, void *stream) {
     if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    if (!seg_ok(dims, seg_offsets, n_seg) || !csr_ok(dims, n_seg, A)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A);
-    // the same call in planning mode first: a workspace or ctx arena smaller than this call takes is
-    // refused before anything is launched (never a launch over the end of a caller buffer)
-    Arena Pc(nullptr, 0), Pw(nullptr, 0);
-    layer_fwd(D, w, s, X, X2, Pc, Pw, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
-    if (Pw.used > (ws ? ws_bytes : 0) || (ctx && Pc.used > ctx_bytes)) return U2GNN_E_ARG;
-    static char empty_ws alignas(256)[256];   // a null base would mean "plan only"
-    Arena C(ctx, ctx_bytes), W(ws ? ws : empty_ws, ws ? ws_bytes : 0);
-    return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    if (!pattern_ok(D, false)) return U2GNN_E_ARG;
+    return plan_then_run(ctx, ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
+        return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
+    });
 }
 
 int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
@@ -992,16 +932,13 @@ int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
                         int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream) {
     if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    if (!seg_ok(dims, seg_offsets, n_seg) || !csr_ok(dims, n_seg, A)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A);
-    Arena Pc(nullptr, 0), Pw(nullptr, 0);   // planning pass with this call's schedule (see u2gnn_layer_fwd)
-    layer_bwd(D, w, s, X, Pc, dX2, dX, g, Pw, reinterpret_cast<hipStream_t>(stream),
-              reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
-    if (Pw.used > (ws ? ws_bytes : 0) || Pc.used > ctx_bytes) return U2GNN_E_ARG;
-    static char empty_ws alignas(256)[256];
-    Arena C(const_cast<void *>(ctx), ctx_bytes), W(ws ? ws : empty_ws, ws ? ws_bytes : 0);
-    return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    if (!pattern_ok(D, false)) return U2GNN_E_ARG;
+    // (planned with this call's schedule: its streams and whether dX is wanted)
+    return plan_then_run(const_cast<void *>(ctx), ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
+        return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
+                         reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
+    });
 }
 
 int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,

@@ -60,16 +60,9 @@ def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = 
     if r is None:
         c, f, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         dims = _dims(N, d, ff, prec, deep_wgrad, window)
-        if nnz:
-            check(hip_lib().u2gnn_layer_sizes_csr(ctypes.byref(dims), float(p_drop), 1 if segments else 0, int(nnz),
-                                                  ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
-                  "u2gnn_layer_sizes_csr")
-        elif segments:
-            check(hip_lib().u2gnn_layer_sizes_seg(ctypes.byref(dims), float(p_drop), 1, ctypes.byref(c),
-                                                  ctypes.byref(f), ctypes.byref(b)), "u2gnn_layer_sizes_seg")
-        else:
-            check(hip_lib().u2gnn_layer_sizes(ctypes.byref(dims), float(p_drop), ctypes.byref(c), ctypes.byref(f),
-                                              ctypes.byref(b)), "u2gnn_layer_sizes")
+        check(hip_lib().u2gnn_layer_sizes_csr(ctypes.byref(dims), float(p_drop), 1 if segments else 0, int(nnz),
+                                              ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
+              "u2gnn_layer_sizes_csr")
         r = _SIZES[key] = (c.value, f.value, b.value)
     return r
 
@@ -112,6 +105,16 @@ def _stream(s=None):
     return ctypes.c_void_p((s or torch.cuda.current_stream()).cuda_stream)
 
 
+def _shared_args(dims, packed, p, prec, deep_wgrad, window, p_drop, seeds, X, segments, adjacency, dev):
+    """What u2gnn_layer_fwd_csr and u2gnn_layer_bwd_csr take alike: (dims, params, seeds, X) in front, and the
+    attention pattern (segment offsets, their count, the CSR) that goes before the streams -- NULL, 0, NULL for a
+    layer with neither, which is the plain u2gnn_layer_fwd / u2gnn_layer_bwd call."""
+    dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(p_drop, seeds)
+    sp, ns = _segments(segments, dev)
+    return ((ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr()),
+            (sp, ns, _adjacency(adjacency, dev) if adjacency is not None else None))
+
+
 def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int, int], need_ctx: bool,
                   prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None, adjacency=None):
     """window = 0: attention over all dims.N rows; W: within each node's window of W token rows
@@ -125,22 +128,9 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
     X2 = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32)
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
-    dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(pd, seeds)
-    if adjacency is not None:
-        sp, ns = _segments(segments, dev)
-        check(hip_lib().u2gnn_layer_fwd_csr(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
-                                            X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                            ws.data_ptr(), ws.numel(), sp, ns, _adjacency(adjacency, dev), _stream()),
-              "u2gnn_layer_fwd_csr")
-    elif segments is not None:
-        sp, ns = _segments(segments, dev)
-        check(hip_lib().u2gnn_layer_fwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
-                                            X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                            ws.data_ptr(), ws.numel(), sp, ns, _stream()), "u2gnn_layer_fwd_seg")
-    else:
-        check(hip_lib().u2gnn_layer_fwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr(),
-                                        X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                        ws.data_ptr(), ws.numel(), _stream()), "u2gnn_layer_fwd")
+    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, window, pd, seeds, X, segments, adjacency, dev)
+    check(hip_lib().u2gnn_layer_fwd_csr(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                        ws.data_ptr(), ws.numel(), *pattern, _stream()), "u2gnn_layer_fwd_csr")
     ctx = None
     if need_ctx:
         ctx = NativeCtx()
@@ -166,27 +156,13 @@ def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: 
     dev = dX2.device
     dX = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32) if need_dx else None
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
-    dd = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, ctx.window)
-    pp, ss = _params(packed, p), _seeds(ctx.p_drop, ctx.seeds)
+    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, ctx.window, ctx.p_drop, ctx.seeds, ctx.X, segments,
+                                 adjacency, dev)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
-    if adjacency is not None:
-        sp, ns = _segments(segments, dev)
-        check(hip_lib().u2gnn_layer_bwd_csr(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
-                                            ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None,
-                                            ctypes.byref(gg), ws.data_ptr(), ws.numel(), sp, ns,
-                                            _adjacency(adjacency, dev), _stream(),
-                                            _stream(side) if side is not None else None), "u2gnn_layer_bwd_csr")
-    elif segments is not None:
-        sp, ns = _segments(segments, dev)
-        check(hip_lib().u2gnn_layer_bwd_seg(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
-                                            ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None,
-                                            ctypes.byref(gg), ws.data_ptr(), ws.numel(), sp, ns, _stream(),
-                                            _stream(side) if side is not None else None), "u2gnn_layer_bwd_seg")
-    else:
-        check(hip_lib().u2gnn_layer_bwd(ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), ctx.X.data_ptr(),
-                                        ctx.buf.data_ptr(), cb, dX2.data_ptr(), dX.data_ptr() if need_dx else None, ctypes.byref(gg),
-                                        ws.data_ptr(), ws.numel(), _stream(), _stream(side) if side is not None else None),
-              "u2gnn_layer_bwd")
+    check(hip_lib().u2gnn_layer_bwd_csr(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
+                                        dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(), ws.numel(),
+                                        *pattern, _stream(), _stream(side) if side is not None else None),
+          "u2gnn_layer_bwd_csr")
     if side is not None:
         for t in (ws, ctx.buf, ctx.X, dX2):
             t.record_stream(side)

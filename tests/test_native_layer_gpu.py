@@ -64,6 +64,54 @@ def test_native_layer_matches_python_orchestration(N, d, ff, prec, train, side):
         assert torch.equal(a, b), name
 
 
+def test_plain_and_seg_exports_match_the_csr_entry_points():
+    """native.py calls only u2gnn_layer_{fwd,bwd}_csr; u2gnn_layer_fwd / u2gnn_layer_bwd and the _seg pair with
+    NULL, 0 are the same call: output, dX and all twelve parameter gradients bit for bit."""
+    import ctypes
+
+    from u2gnn_hip import _lib
+    N, d, ff, prec = 300, 67, 128, "bf16x3"
+    layer = _layer(d, ff, 5)
+    p = LayerParams.from_encoder_layer(layer)
+    dims = Dims(N, d, ff)
+    packed = PackedLayer(d, ff, "cuda")
+    packed.pack(p)
+    seeds = {s: site_seed(77, 0, 1, s) for s in (SITE_ATTN, SITE_DROP1, SITE_DROPFF, SITE_DROP2)}
+    g = torch.Generator(device="cuda").manual_seed(3)
+    X = torch.zeros(dims.Np, dims.dp, device="cuda")
+    X[:N, :d] = torch.randn(N, d, device="cuda", generator=g)
+    dY = torch.zeros(dims.Np, dims.dp, device="cuda")
+    dY[:N, :d] = torch.randn(N, d, device="cuda", generator=g)
+
+    Y_ref, ctx = native.layer_forward(X, packed, p, dims, True, seeds, True, prec, 0.5)
+    g_ref = _zeros_like_params(p)
+    dX_ref = native.layer_backward(dY, ctx, packed, p, g_ref, dims, prec)
+
+    lib, by = _lib.hip_lib(), ctypes.byref
+    cb, fb, bb = native.sizes(N, d, ff, prec, 0.5)
+    dd, pp, ss = native._dims(N, d, ff, prec, True), native._params(packed, p), native._seeds(0.5, seeds)
+    for name, fwd, bwd, seg in (("plain", lib.u2gnn_layer_fwd, lib.u2gnn_layer_bwd, ()),
+                                ("seg", lib.u2gnn_layer_fwd_seg, lib.u2gnn_layer_bwd_seg, (None, 0))):
+        Y, dX = torch.empty_like(Y_ref), torch.empty_like(dX_ref)
+        buf = torch.empty(cb, device="cuda", dtype=torch.uint8)
+        ws_f = torch.empty(max(256, fb), device="cuda", dtype=torch.uint8)
+        ws_b = torch.empty(max(256, bb), device="cuda", dtype=torch.uint8)
+        g_exp = _zeros_like_params(p)
+        gg = _lib.LayerGrads(*[getattr(g_exp, k).data_ptr() for k in _lib._PKEYS])
+        _lib.check(fwd(by(dd), by(pp), by(ss), X.data_ptr(), Y.data_ptr(), buf.data_ptr(), cb, ws_f.data_ptr(),
+                       ws_f.numel(), *seg, native._stream()), "forward, " + name)
+        _lib.check(bwd(by(dd), by(pp), by(ss), X.data_ptr(), buf.data_ptr(), cb, dY.data_ptr(), dX.data_ptr(), by(gg),
+                       ws_b.data_ptr(), ws_b.numel(), *seg, native._stream(), None), "backward, " + name)
+        torch.cuda.synchronize()
+        assert torch.equal(Y, Y_ref), name
+        assert torch.equal(dX, dX_ref), name
+        got, want = g_exp.tensors(), g_ref.tensors()
+        assert len(got) == len(want) == 12
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert torch.isfinite(a).all(), (name, k)
+            assert torch.equal(a, b), (name, k)
+
+
 def test_native_forward_without_ctx_matches():
     N, d, ff = 500, 67, 128
     layer = _layer(d, ff, 9)
