@@ -3,10 +3,9 @@
 // streams, one C-ABI call per layer instead of ~40 Python-side launches.
 //
 // Reference: pytorch_U2GNN_Sup.py:19-21,35 (UnSup: pytorch_U2GNN_UnSup.py:37-40,57) reach this
-// through torch.nn.TransformerEncoder; the Python orchestration of the same kernels is
-// u2gnn_hip/engine.py (encoder_layer_forward / encoder_layer_backward), which this file mirrors
-// launch for launch (same tiles, split counts and reduction order, hence bit-identical results:
-// tests/test_native_layer_gpu.py).
+// through torch.nn.TransformerEncoder.  u2gnn_hip/engine.py issues the same kernels from Python, one call per
+// launch, and takes every tile, split count and threshold from layer_plan / split_plan below
+// (u2gnn_layer_plan, u2gnn_gemm_split_plan), hence bit-identical results: tests/test_native_layer_gpu.py.
 //
 // Memory: every buffer is caller-allocated.  The forward writes the tensors saved for the
 // backward into a "ctx" arena and uses a scratch workspace for S and split-K slabs; the backward
@@ -32,8 +31,7 @@ namespace {
 
 inline int64_t rup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// padded rows: multiples of 256 from 1024 rows on (the N^2 products always get 256x128 blocks),
-// else of 128 (mirrors engine.row_pad)
+// padded rows: multiples of 256 from 1024 rows on (the N^2 products always get 256x128 blocks), else of 128
 inline int64_t rows_pad(int64_t N) { return N >= 1024 ? rup(N, 256) : rup(N, 128); }
 
 struct Dims {
@@ -136,10 +134,10 @@ struct Ctx {   // tensors saved by the forward for the backward
 };
 
 // node attention for d <= 32 on the vector ALUs (u2gnn_attn_small_*, small_layer.hip): every precision, no
-// N x N image (engine.small_attn mirrors the rule)
+// N x N image -- the matrix-core products would be >= 50 % padding (dp = 64)
 bool small_attn(const Dims &D) { return !D.window && !sparse_attn(D) && D.d <= 32; }
 // the forward tail (a3.3 + a3.4) of a mid-width layer with few rows as one row-block kernel + the slab LayerNorm
-// (mid_layer.hip; C2: 2 launches instead of 5); engine.mid_tail mirrors the rule
+// (mid_layer.hip; C2: 2 launches instead of 5)
 bool mid_tail(const Dims &D) { return !D.window && !sparse_attn(D) && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
 
 Ctx carve_ctx(Arena &A, const Dims &D) {
@@ -186,8 +184,9 @@ void probe_mark(int role, bool end, hipStream_t st, bool plan) {
     if (end) ++g_probe.n;
 }
 
-// f16x3 operand pre-scale exponents (u2gnn_hip.h h3_exp_a / h3_exp_b; kernels.H3_EXP / h3_prob_exp mirror them):
-// activations and weights by 2^6, the probability image (entries ~1/N, at most 1/(1-p)) by 2^(15 - ceil(log2(1/(1-p))))
+// f16x3 operand pre-scale exponents (u2gnn_hip.h h3_exp_a / h3_exp_b): activations and weights (typical magnitudes
+// 2^-5 .. 2^0) by 2^6; the probability image (entries ~1/N, at most 1/(1-p)) by 2^(15 - ceil(log2(1/(1-p)))), so
+// that its largest entry stays below fp16's 65504 and its typical ones keep 22 bits
 constexpr int32_t kH3Exp = 6;
 int32_t h3_prob_exp(float pd) {
     int32_t e = 15;
@@ -199,7 +198,7 @@ struct G {   // one GEMM product (defaults = plain store): the launch arguments 
     u2gnn_gemm_args a;
     int probe_role = 0;        // U2GNN_ROLE_*: the launch is bracketed by the probe's events
     bool accumulate = false;   // gemm_split: C += the product
-    bool deep_k = false;       // gemm_split: weight gradient (16-deep K step, <= 8 slabs)
+    bool deep_k = false;       // gemm_split: weight gradient (split_plan: 16-deep K step, capped slabs)
     const int64_t *rblk = nullptr, *cblk = nullptr;   // gemm_split: {padded, real} block of C's rows / columns
     G(const float *A, const float *B, float *C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
       int64_t ldc, int prec) {
@@ -283,62 +282,60 @@ struct To {   // where a gemm_split product goes (defaults = launched and comple
     hipStream_t st;
     Defer *held = nullptr;    // non-null: the launch and its slab reduce join this list's flush instead
     Slabs *slabs = nullptr;   // non-null: a split product leaves its slabs here instead of reducing them
+    bool grouped = false;     // one of two products that share the grouped launch (dQ, dK)
     explicit To(hipStream_t s) : st(s) {}
     To &hold(Defer *df) { held = df; return *this; }
+    To &pair() { grouped = true; return *this; }
     To &leave_slabs(Slabs *s) { slabs = s; return *this; }
 };
 
-// split-K block targets (engine._gemm_split): 448 blocks for 64 / 128 tiles, 240 for 256x128 tiles
-// (round-2 sweeps: 224 / 896 within noise, 120 / 300 / 460 slower on the 256x128 products)
+// How gemm_split runs one product C[M,N] (+)= op(A) op(B) of depth Kd (u2gnn_hip.h u2gnn_split_plan): when the tile
+// grid alone would leave most of the 256 CUs idle (skinny outputs with a deep node dimension: P.V, Pd^T.dO, dS.K,
+// dS^T.Q, the weight gradients, dH.W1, dQKV.W_in) the depth is cut into fp32 slabs of >= 4 K steps.  Block targets:
+// 448 for 64 / 128 tiles, 240 for 256x128 tiles (round-2 sweeps: 224 / 896 within noise, 120 / 300 / 460 slower on
+// the 256x128 products).
+struct SplitPlan {
+    bool direct;
+    int tile, launch_tile;
+    int64_t split;
+};
 constexpr int64_t kSplitTarget = 448, kSplitTarget256 = 240;
 
-// engine._gemm_split: deterministic split-K into fp32 slabs + one reduce pass (alpha, accumulate,
-// padded->real block map).  g describes the finished product (its C, ldc, alpha and accumulate are the
-// result's; deep = weight gradient: 16-deep K step, <= 8 slabs), `to` where it goes.
-int gemm_split(Arena &W, const Dims &D, G g, const To &to) {
-    const int64_t M = g.a.M, N = g.a.N, Kd = g.a.K;
-    const int role = g.probe_role;
-    const bool accumulate = g.accumulate, deep = g.deep_k;
-    hipStream_t st = to.st;
-    Defer *df = to.held;
-    const bool f32 = g.a.precision == U2GNN_PREC_F32;
+SplitPlan split_plan(int64_t M, int64_t N, int64_t Kd, int prec, bool accumulate, bool deep, bool mapped, bool grouped,
+                     bool deep_wgrad, bool held) {
+    const bool f32 = prec == U2GNN_PREC_F32;
     const int64_t bk = f32 ? 16 : 32;
-    const bool plan = W.plan();
-    const bool mapped = g.rblk != nullptr;
-    g.epi(accumulate ? U2GNN_EPI_ACCUM : U2GNN_EPI_STORE);   // (the slab exit stores; its reduce accumulates)
     // (tiny: an accumulating product of at most 16 tiles and 16 K steps -- C2's dX += dQKV W_in, 4 tiles --
-    // runs as one short launch instead of 3 split-K blocks + a reduce launch; engine._gemm_split mirrors it)
+    // runs as one short launch instead of 3 split-K blocks + a reduce launch)
     const bool tiny = accumulate && Kd <= 512 && (M / 64) * (N / 64) <= 16;
     if (!f32 && !deep && !mapped && Kd <= 2048 && M % 64 == 0 && N % 64 == 0 &&
         ((M / 64) * (N / 64) >= 256 || tiny)) {
         // shallow K (dH.W1, dQKV.W_in) with enough 64x64 tiles to fill the chip: no split, the
         // epilogue accumulates straight into C (no slabs, no reduce pass)
         const bool big = M % 256 == 0 && N % 128 == 0 && (M / 256) * (N / 128) >= U2GNN_BIG_TILE_BLOCKS;
-        return g.tile(big ? 256 : 64).run(st, plan);
+        return {true, big ? 256 : 64, big ? 256 : 64, 1};
     }
     int t;
     int64_t tiles, target = kSplitTarget;
     if (!f32 && M % 256 == 0 && N % 128 == 0 && (M / 256) * (N / 128) >= 32) {
+        // 256x128 blocks (8 waves, one block per CU): the skinny attention products
         t = 256, tiles = (M / 256) * (N / 128), target = kSplitTarget256;
         // dQ and dK go out as ONE grouped launch: half the block target each, so the launch holds ~240 blocks
         // (C4: split 2, 228 blocks instead of split 4 and 456; 3.016-3.017 vs 3.054-3.065 ms per step in one
         // session, profiles/r04/ab_sched.txt; split 1 and 128x128 tiles at split 2 were slower)
-        if (role == U2GNN_ROLE_DQ || role == U2GNN_ROLE_DK) target = kSplitTarget256 / 2;
+        if (grouped) target = kSplitTarget256 / 2;
     } else {
         t = (M % 128 == 0 && N % 128 == 0) ? 128 : 64;
         tiles = (M / t) * (N / t);
     }
-    int64_t split = target / (tiles > 0 ? tiles : 1);
-    if (Kd / (4 * bk) < split) split = Kd / (4 * bk);
-    if (split < 1) split = 1;
-    // slab cap of the weight gradients (engine.wgrad_split_cap): 8 for node-sized depths, 16 for
-    // token-sized ones (neighbour mode, K = N(k+1) rows)
-    const int64_t wgrad_split_max = Kd <= 8192 ? 8 : 16;
-    if (deep && D.deep_wgrad && !f32 && t == 128) {
+    int64_t split = std::max<int64_t>(1, std::min(target / std::max<int64_t>(tiles, 1), Kd / (4 * bk)));
+    if (deep && deep_wgrad && !f32 && t == 128) {
+        // weight gradients (a few dozen 128x128 output tiles, K = the rows): the 16-deep K step runs 3 blocks per
+        // CU.  Slab cap: at node-sized depths 8 slabs move half the bytes of 16 beside the main stream (C4 3.236 /
+        // 3.238 vs 3.251 / 3.260 ms; 12: 3.26, 4: 3.27); token-sized depths (neighbour mode, K = N(k+1) rows) keep
+        // 16 (8: 15.2 vs 13.9 ms)
         t = 129;
-        split = target / (tiles > 0 ? tiles : 1);
-        if (split > wgrad_split_max) split = wgrad_split_max;
-        if (split < 1) split = 1;
+        split = std::max<int64_t>(1, std::min<int64_t>(target / std::max<int64_t>(tiles, 1), Kd <= 8192 ? 8 : 16));
     }
     // a held-back product joins its layer's grouped launch, whose kernels are the 64x64, 16-deep 128x128 and
     // 256x128 ones: a 128x128 job runs there as four 64x64 tiles (the split is chosen above, so the sums and
@@ -346,8 +343,25 @@ int gemm_split(Arena &W, const Dims &D, G g, const To &to) {
     // A launch of fewer than 64 blocks of 128x128 runs them as 64x64 tiles too (4x the blocks for the same
     // sums; C2's dX1 = dH W1: 8 blocks of a 4-step K loop, 8.6 us)
     // (bf16 precisions, whose 64x64 and 128x128 kernels form the same k-ordered sums)
-    const int t_group = (!f32 && t == 128 && (df || (M / 128) * (N / 128) * split < 64)) ? 64 : t;
-    g.tile(t_group);
+    const bool lower = !f32 && t == 128 && (held || (M / 128) * (N / 128) * split < 64);
+    return {false, t, lower ? 64 : t, split};
+}
+
+// deterministic split-K into fp32 slabs + one reduce pass (alpha, accumulate, padded->real block map), as
+// split_plan decides.  g describes the finished product (its C, ldc, alpha and accumulate are the result's;
+// deep = weight gradient), `to` where it goes.
+int gemm_split(Arena &W, const Dims &D, G g, const To &to) {
+    const int64_t M = g.a.M, N = g.a.N;
+    const bool accumulate = g.accumulate, mapped = g.rblk != nullptr;
+    hipStream_t st = to.st;
+    Defer *df = to.held;
+    const bool plan = W.plan();
+    const SplitPlan sp = split_plan(M, N, g.a.K, g.a.precision, accumulate, g.deep_k, mapped, to.grouped, D.deep_wgrad,
+                                    df != nullptr);
+    const int64_t split = sp.split;
+    g.epi(accumulate ? U2GNN_EPI_ACCUM : U2GNN_EPI_STORE);   // (the slab exit stores; its reduce accumulates)
+    g.tile(sp.launch_tile);
+    if (sp.direct) return g.run(st, plan);
     if (split == 1 && !mapped) {
         if (df && !accumulate) {
             df->hold(g);
@@ -379,7 +393,7 @@ int gemm_split(Arena &W, const Dims &D, G g, const To &to) {
                              j.dst, j.ld_dst, j.alpha, j.accumulate, st);
 }
 
-// engine._wgrad: dst(real) = unpack(dY^T X), held back to df's flush
+// dst(real) = unpack(dY^T X), held back to df's flush
 int wgrad(Arena &W, const Dims &D, const float *dY, int64_t ld_dy, const float *X, int64_t ld_x, int64_t m_pad,
           int64_t n_pad, float *dst, int64_t ld_dst, const int64_t *rblk, const int64_t *cblk, hipStream_t st,
           Defer *df) {
@@ -481,11 +495,9 @@ void set_ln(u2gnn_gemm_args &a, const float *gamma, const float *beta, float *y,
     a.ln_mean = mean, a.ln_rstd = rstd, a.ln_d = d, a.ln_rows = rows, a.ln_eps = 1e-5f;
 }
 
-// the fused attention forward (u2gnn_attn_softmax_pv): node-axis attention in the matrix-core
-// precisions with dp <= 384 (engine.fused_attn mirrors the rule)
 // split-K depth of FFN2 in the matrix-core precisions (mfma), dp <= 256: with fewer than 128 output
 // tiles of 64x64, aim at ~256 blocks of >= 4 K steps; u2gnn_slab_bias_drop_resid_ln then forms the bias,
-// dropout, residual and LayerNorm2 (engine.ffn2_split mirrors the rule).  dp = 64 (C5 and the other
+// dropout, residual and LayerNorm2.  dp = 64 (C5 and the other
 // fused-LayerNorm layers) since round 3; dp <= 256 since round 5: C2's IMDBBINARY batches (Np = 128,
 // dp = 192) ran FFN2 as 6 blocks of a 32-step K loop, 16 us, plus a LayerNorm launch
 int64_t ffn2_split(int64_t dp, bool mfma, int64_t Np, int64_t ffp) {
@@ -497,23 +509,53 @@ int64_t ffn2_split(int64_t dp, bool mfma, int64_t Np, int64_t ffp) {
 }
 
 // tile of S = Q K^T: 256x128 blocks unless they would leave most CUs idle (C5's Np = 2048 gives 128 of
-// them), then 128x128 (the same per-element sums: same bits; engine.qk_tile mirrors the rule)
+// them), then 128x128 (the same per-element sums: same bits)
 int qk_tile(int64_t Np) { return (Np % 256 == 0 && (Np / 256) * (Np / 128) >= 256) ? 256 : 128; }
+// ... and in the three-pass attention forward: 256x128 blocks where the rows allow, else the GEMM's own rule
+int qk_tile_3pass(const Dims &D) { return (D.prec_fwd != U2GNN_PREC_F32 && D.Np % 256 == 0) ? 256 : 0; }
+// tile of the in-projection: 256x128 blocks from 3 waves of them on (token-sized rows, neighbour mode), the GEMM's
+// own rule below that: C4's 19 x 9 blocks of 256x128 leave a third of the CUs idle, its 76 x 18 64-tile blocks run
+// the step 0.8 % faster (3/3 reps, profiles/r02/qkv_tile_ab.txt; bit-identical)
+int in_proj_tile(const Dims &D) {
+    return (D.prec_fwd != U2GNN_PREC_F32 && D.Np % 256 == 0 &&
+            (D.Np / 256) * (3 * D.dp / 128) >= U2GNN_BIG_TILE_BLOCKS) ? 256 : 0;
+}
+// LayerNorm forward inside the bias-dropout-residual GEMM epilogue: one 64-column tile holds whole rows (d <= 64),
+// matrix-core precisions
+bool fused_ln(const Dims &D) { return D.dp == 64 && D.prec_fwd != U2GNN_PREC_F32; }
+// one-stream layers in the matrix-core precisions: LayerNorm1's backward forms the attention backward's delta =
+// rowsum(dO * O); the fp32 parity path keeps u2gnn_rowdot, whose error does not grow with |X|
+bool ln1_forms_delta(const Dims &D) { return !D.window && !sparse_attn(D) && D.prec != U2GNN_PREC_F32; }
 
+// the fused attention forward (u2gnn_attn_softmax_pv): node-axis attention in the matrix-core precisions with
+// dp <= 384 and at least kFusedMinNp padded rows
 // (f16x3 -- the fwdh policy -- runs fused: V as fp16 x2 rows from the in-projection, 3.024 vs 3.052 ms three-pass,
 // profiles/r06/h3g_fused_ab.txt; bf16x6 -- the fwd6 policy -- keeps the three-pass form: its fused kernel, ran
 // the C4 step at 3.42 / 3.43 ms against 3.40 unfused, and its exp2-based probabilities moved one boundary ReLU unit
 // of the test seed's step across 0).  Few rows (C2's IMDBBINARY batches, Np = 128: ONE
 // workgroup walks every key) run the three-pass form, whose GEMM tiles spread over more CUs: C2 fwdh 0.424 ms
-// three-pass (r6h) vs 0.460 fused (r6i); engine.FUSED_MIN_NP mirrors the bound
+// three-pass (r6h) vs 0.460 fused (r6i)
 constexpr int64_t kFusedMinNp = 1024;
 bool fused_attn(const Dims &D) {
     return D.Np >= kFusedMinNp && !D.window && !sparse_attn(D) && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 &&
            D.prec_fwd != U2GNN_PREC_BF16X6 && D.dp <= 384;
 }
 
+// every shape rule of the node-axis (or window) layer in one place: what u2gnn_layer_plan hands out
+u2gnn_layer_rules layer_plan(const Dims &D, float p_drop) {
+    u2gnn_layer_rules p;
+    std::memset(&p, 0, sizeof(p));
+    p.rows_pad = D.Np, p.dp = D.dp, p.ffp = D.ffp;
+    p.ffn2_split = ffn2_split(D.dp, D.prec_fwd != U2GNN_PREC_F32, D.Np, D.ffp);
+    p.small_attn = small_attn(D), p.mid_tail = mid_tail(D), p.fused_attn = fused_attn(D);
+    p.qk_tile = qk_tile(D.Np), p.qk_tile_3pass = qk_tile_3pass(D), p.in_proj_tile = in_proj_tile(D);
+    p.fused_ln = fused_ln(D), p.ln_delta = ln1_forms_delta(D);
+    p.h3_exp = kH3Exp, p.h3_prob_exp = h3_prob_exp(p_drop);
+    return p;
+}
+
 // the row-local tail of a small-width layer (u2gnn_layer_tail_small_*, small_layer.hip): every precision when the
-// attention is the small-width one (engine.small_attn mirrors the rule)
+// attention is the small-width one
 u2gnn_small_tail_args tail_args(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s, const Ctx &c,
                                 const float *X, float *X2) {
     u2gnn_small_tail_args t;
@@ -545,12 +587,7 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     // a3.1 in-projection (+bias, Q scaled by 1/sqrt(d)); the small-width attention does its own
     if (!small_attn(D)) {
         G g(X, w->W_in, c.QKV, Np, 3 * dp, dp, dp, dp, 3 * dp, prec);
-        // 256x128 blocks from 3 waves of them on (token-sized rows, neighbour mode), the default tile
-        // rule below that: C4's 19 x 9 blocks of 256x128 leave a third of the CUs idle, its 76 x 18 64-tile
-        // blocks run the step 0.8 % faster (3/3 reps, profiles/r02/qkv_tile_ab.txt; bit-identical).
-        const int qkv_tile = (prec != U2GNN_PREC_F32 && Np % 256 == 0 &&
-                              (Np / 256) * (3 * dp / 128) >= U2GNN_BIG_TILE_BLOCKS) ? 256 : 0;
-        g.tb().epi(U2GNN_EPI_BIAS).tile(qkv_tile);
+        g.tb().epi(U2GNN_EPI_BIAS).tile(in_proj_tile(D));
         g.a.bias = w->b_in;
         g.a.alpha = (float)(1.0 / std::sqrt((double)d));
         g.a.scale_cols = dp;
@@ -608,7 +645,7 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         float *S = W.take<float>(Np * Np);
         {
             G g(Q, Kt, S, Np, Np, dp, 3 * dp, 3 * dp, Np, prec);
-            g.tb().tile((prec != U2GNN_PREC_F32 && Np % 256 == 0) ? 256 : 0).role(U2GNN_ROLE_QK);
+            g.tb().tile(qk_tile_3pass(D)).role(U2GNN_ROLE_QK);
             U2GNN_TRY(g.run(st, plan));
         }
         if (!plan)
@@ -629,9 +666,8 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
             U2GNN_TRY(u2gnn_layer_tail_mid_fwd(&t, mws, wsf, st));
         }
     } else {
-        // a3.3 out-projection + dropout1 + residual, LayerNorm1 (fused into the GEMM epilogue when a
-        // 64-column tile holds whole rows: d <= 64, bf16 modes; engine.fused_ln mirrors the rule)
-        const bool fuse_ln = dp == 64 && prec != U2GNN_PREC_F32;
+        // a3.3 out-projection + dropout1 + residual, LayerNorm1
+        const bool fuse_ln = fused_ln(D);
         {
             G g(c.O, w->W_o, c.Z1, Np, dp, dp, dp, dp, dp, prec);
             g.tb().epi(fuse_ln ? U2GNN_EPI_BIAS_DROP_RESID_LN : U2GNN_EPI_BIAS_DROP_RESID);
@@ -698,8 +734,7 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     Defer *df = &defer_p, *att = &defer_a;
     const int64_t blk_d[2] = {dp, d}, blk_ff[2] = {ffp, ff};
     const bool tail = small_attn(D);   // the row-local tail kernel (small_layer.hip) forms dX1 ... dO and delta
-    // one-stream layers in the matrix-core precisions: LayerNorm1's backward forms delta = rowsum(dO * O)
-    const bool ln_delta = !D.window && !sparse_attn(D) && prec != U2GNN_PREC_F32;
+    const bool ln_delta = ln1_forms_delta(D);
     float *dX1 = W.take<float>(Np * dp), *dF = W.take<float>(Np * dp);
     float *dH = W.take<float>(Np * ffp);
     float *dA = W.take<float>(Np * dp);
@@ -821,9 +856,9 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
             U2GNN_TRY(gg.run(st, plan));
         }
         U2GNN_TRY(gemm_split(W, D, G(dS, Kt, dQKV, Np, dp, Np, Np, 3 * dp, 3 * dp, D.prec_ab).alpha(q_scale)
-                                       .role(U2GNN_ROLE_DQ), To(st).hold(att)));
+                                       .role(U2GNN_ROLE_DQ), To(st).hold(att).pair()));
         U2GNN_TRY(gemm_split(W, D, G(dS, Q, dQKV + dp, Np, dp, Np, Np, 3 * dp, 3 * dp, D.prec_ab).ta()
-                                       .role(U2GNN_ROLE_DK), To(st).hold(att)));
+                                       .role(U2GNN_ROLE_DK), To(st).hold(att).pair()));
         U2GNN_TRY(flush(att, W, st));
         U2GNN_TRY(sd.wait(dv_done));   // dV before dX += dQKV W_in
     }
@@ -834,7 +869,7 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     // in_proj_bias: the Q and V thirds are column sums of dQKV; the K third is exactly zero -- a softmax row is
     // invariant to a constant added to its scores, so sum_j dK_j = sum_i Q_i sum_j dS_ij = 0.  The reference's
     // value there is summation noise, which Adam's first step (lr g / (|g| + eps)) turns into moves of up to lr;
-    // a column sum over zero rows writes the exact zeros (engine.in_bias_grad mirrors this)
+    // a column sum over zero rows writes the exact zeros
     bias_grad(df, dQKV, Np, dp, 3 * dp, dp, d, g->in_b);
     bias_grad(df, dQKV + dp, 0, dp, 3 * dp, dp, d, g->in_b + d);
     bias_grad(df, dQKV + 2 * dp, Np, dp, 3 * dp, dp, d, g->in_b + 2 * d);
@@ -954,6 +989,25 @@ int u2gnn_layer_bwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, c
                     const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, void *stream, void *side_stream) {
     return u2gnn_layer_bwd_seg(dims, w, s, X, ctx, ctx_bytes, dX2, dX, g, ws, ws_bytes, nullptr, 0, stream,
                                side_stream);
+}
+
+int u2gnn_layer_plan(const u2gnn_layer_dims *dims, float p_drop, u2gnn_layer_rules *plan) {
+    if (!dims_ok(dims) || !plan || !(p_drop >= 0.f && p_drop < 1.f)) return U2GNN_E_ARG;
+    *plan = layer_plan(make_dims(dims, nullptr, 0, nullptr, 0), p_drop);
+    return U2GNN_OK;
+}
+
+int u2gnn_gemm_split_plan(const u2gnn_split_query *q, u2gnn_split_plan *plan) {
+    if (!q || !plan || q->M < 64 || q->N < 64 || q->K < 16 || q->M % 64 || q->N % 64 || q->K % 16 ||
+        q->precision < U2GNN_PREC_F32 || q->precision > U2GNN_PREC_F16X3)
+        return U2GNN_E_ARG;
+    for (int32_t f : {q->accumulate, q->deep, q->mapped, q->grouped, q->deep_wgrad, q->held})
+        if (f != 0 && f != 1) return U2GNN_E_ARG;
+    const SplitPlan sp = split_plan(q->M, q->N, q->K, q->precision, q->accumulate, q->deep, q->mapped, q->grouped,
+                                    q->deep_wgrad, q->held);
+    std::memset(plan, 0, sizeof(*plan));
+    plan->direct = sp.direct, plan->tile = sp.tile, plan->launch_tile = sp.launch_tile, plan->split = (int32_t)sp.split;
+    return U2GNN_OK;
 }
 
 int u2gnn_probe_arm(int32_t role, int32_t capacity) {

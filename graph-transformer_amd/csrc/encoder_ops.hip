@@ -1583,6 +1583,13 @@ int u2gnn_slab_bias_drop_resid_ln(const float *src, int32_t n_slab, int64_t slab
     return u2gnn_launch_status();
 }
 
+// workspace of the single-job column reductions (u2gnn_colsum, u2gnn_layernorm_bwd_params): three partial rows
+// per CS_ROWS-row group
+int64_t u2gnn_colstat_ws_floats(int64_t rows, int64_t cols_pad) {
+    if (rows < 0 || cols_pad < 0) return -1;
+    return std::max<int64_t>(1, (rows + CS_ROWS - 1) / CS_ROWS) * 3 * cols_pad;
+}
+
 int64_t u2gnn_reduce_batch_ws_floats(const u2gnn_reduce_job *jobs, int32_t n) {
     if (n < 0 || (n && !jobs)) return -1;
     int64_t tot = 0;

@@ -30,7 +30,7 @@ ERRORS = {-1: "bad argument", -2: "misaligned pointer / leading dimension", -3: 
 
 EPI_STORE, EPI_BIAS, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU_DROP, EPI_RELU_DROP_BWD, EPI_ACCUM, EPI_ATTN_DS, \
     EPI_ATTN_DS_SIGNED, EPI_ATTN_DS_RECOMP, EPI_BIAS_DROP_RESID_LN, EPI_STORE_ROWDOT, EPI_STORE_ROWSTAT = range(12)
-ABI_VERSION = 18   # include/u2gnn_hip.h U2GNN_ABI_VERSION
+ABI_VERSION = 19   # include/u2gnn_hip.h U2GNN_ABI_VERSION
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4
 
 
@@ -90,6 +90,23 @@ class LayerDims(ctypes.Structure):
                 ("window", c_int32), ("reserved", c_int32)]
 
 
+class LayerPlan(ctypes.Structure):   # u2gnn_layer_rules (ABI v19)
+    _fields_ = ([(k, c_int64) for k in ("rows_pad", "dp", "ffp", "ffn2_split")] +
+                [(k, c_int32) for k in ("small_attn", "mid_tail", "fused_attn", "qk_tile", "qk_tile_3pass",
+                                        "in_proj_tile", "fused_ln", "ln_delta", "h3_exp", "h3_prob_exp")] +
+                [("reserved", c_int32 * 6)])
+
+
+class SplitQuery(ctypes.Structure):   # u2gnn_split_query (ABI v19)
+    _fields_ = ([(k, c_int64) for k in ("M", "N", "K")] +
+                [(k, c_int32) for k in ("precision", "accumulate", "deep", "mapped", "grouped", "deep_wgrad", "held")] +
+                [("reserved", c_int32 * 5)])
+
+
+class SplitPlan(ctypes.Structure):   # u2gnn_split_plan (ABI v19)
+    _fields_ = [(k, c_int32) for k in ("direct", "tile", "launch_tile", "split")] + [("reserved", c_int32 * 4)]
+
+
 _PKEYS = ("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b")
 
 
@@ -139,6 +156,9 @@ _HIP_SIGS = {
     "u2gnn_gemm": ([POINTER(GemmArgs), VP], c_int32),
     "u2gnn_gemm_group": ([POINTER(GemmArgs), I32, VP], c_int32),
     "u2gnn_reduce_batch_ws_floats": ([POINTER(ReduceJob), I32], I64),
+    "u2gnn_colstat_ws_floats": ([I64, I64], I64),
+    "u2gnn_layer_plan": ([POINTER(LayerDims), F32, POINTER(LayerPlan)], c_int32),
+    "u2gnn_gemm_split_plan": ([POINTER(SplitQuery), POINTER(SplitPlan)], c_int32),
     "u2gnn_reduce_batch": ([POINTER(ReduceJob), I32, VP, I64, VP], c_int32),
     "u2gnn_concat_dropout": ([POINTER(c_void_p), I32, I64, I64, I64, F32, c_uint64, VP, I64, VP], c_int32),
     "u2gnn_split_dropout_bwd": ([VP, I64, I32, I64, I64, I64, I64, F32, c_uint64, POINTER(c_void_p), VP], c_int32),

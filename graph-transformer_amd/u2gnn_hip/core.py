@@ -243,6 +243,9 @@ class EncoderStack:
             raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
         self.packed = None
+        # Python orchestration only: the three-pass attention forward where the fused kernel would run
+        # (tools/prec_train_probe.py)
+        self.three_pass = False
         # optional callable(prefix, stream): called once a layer's parameter gradients are
         # enqueued (on `stream`), e.g. dp.OverlappedGradAllReduce.layer_done
         self.grad_ready = None
@@ -304,7 +307,7 @@ class EncoderStack:
                                                 segments=segments, adjacency=adjacency)
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
-                                                 need_ctx, self.prec, self.p_enc)
+                                                 need_ctx, self.prec, self.p_enc, three_pass=self.three_pass)
                 lctx.append(c)
             outs.append(X)
             lctxs.append(lctx)

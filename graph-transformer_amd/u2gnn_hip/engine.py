@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
+from . import native
 
 E = _lib
 
@@ -38,7 +39,7 @@ def rup(x: int, m: int) -> int:
 
 def row_pad(N: int) -> int:
     """Padded node rows: multiples of 256 from 1024 rows on (the N^2 products then always run on
-    256x128 blocks), else of 128.  Mirrors rows_pad() in csrc/encoder_layer.cpp."""
+    256x128 blocks), else of 128 (native.layer_plan(...).rows_pad: tests/test_host_cpu.py holds the two equal)."""
     return rup(N, 256) if N >= 1024 else rup(N, 128)
 
 
@@ -185,19 +186,6 @@ def side_stream(dev: torch.device) -> "torch.cuda.Stream":
 SIDE_MIN_ELEMS = int(os.environ.get("U2GNN_SIDE_MIN_ELEMS", 1 << 20))   # (env: A/B experiments only)
 
 
-def fused_ln(dp: int, prec: str) -> bool:
-    """LayerNorm forward inside the bias-dropout-residual GEMM epilogue: d <= 64 (one 64-column tile
-    per row), matrix-core precisions (encoder_layer.cpp applies the same rule)."""
-    return dp == 64 and prec != "fp32"
-
-
-def ln_delta(prec: str) -> bool:
-    """The attention backward's delta = rowsum(dO * O) from LayerNorm1's backward
-    (layernorm_bwd_delta) in the matrix-core precisions; the fp32 parity path keeps its own rowdot
-    launch, whose error does not grow with |X| (encoder_layer.cpp applies the same rule)."""
-    return prec != "fp32"
-
-
 def side_stream_pays(dims: "Dims") -> bool:
     return dims.Np * dims.dp >= SIDE_MIN_ELEMS
 
@@ -224,16 +212,6 @@ class OffPath:
     def join(self):
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
-
-
-BIG_TILE_BLOCKS = 768
-# slab cap of the deep weight-gradient products (encoder_layer.cpp applies the same rule): at node-sized
-# depths 8 slabs move half the bytes of 16 beside the main stream (C4 3.236 / 3.238 vs 3.251 / 3.260 ms;
-# 12: 3.26, 4: 3.27); token-sized depths (neighbour mode, K = 82 K rows) keep 16 (8: 15.2 vs 13.9 ms).
-
-
-def wgrad_split_cap(kd: int) -> int:
-    return 8 if kd <= 8192 else 16
 
 
 # Precision experiments (Python orchestration only): products (by role) that run plain bf16 when the
@@ -274,48 +252,26 @@ def _rp(role: str, prec: str) -> str:
     return "bf16" if (prec == "bf16x3" and role in ROLE_BF16) else prec
 
 
-def _gemm_split(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=False, trans_b=False, alpha=1.0, accumulate=False,
-                prec="fp32", rblk=None, cblk=None, target=448, flops=None, deep=False, clamp_a=False, target256=240,
-                h3_exp=None):
-    """C (+)= alpha * op(A) . op(B) with deterministic split-K: when the tile grid alone would
-    leave most of the 256 CUs idle (skinny outputs with a deep node dimension: P.V, Pd^T.dO,
-    dS.K, dS^T.Q, the weight gradients, dH.W1, dQKV.W_in), the depth is cut into fp32 slabs
-    (>= 4 K-tiles each, ~target workgroups) and one streaming pass sums them into C — applying
-    alpha, accumulation and an optional padded->real block map (rblk, cblk).  clamp_a: A is the
-    signed probability image (read as Pd).  h3_exp: the f16x3 operand pre-scales (kernels.gemm)."""
-    bk = 16 if prec == "fp32" else 32
-    # tiny: an accumulating product of <= 16 tiles and <= 16 K steps (C2's dX += dQKV W_in) as one short launch
-    tiny = accumulate and Kd <= 512 and (M // 64) * (N // 64) <= 16
-    if (prec != "fp32" and not deep and rblk is None and Kd <= 2048 and M % 64 == 0
-            and N % 64 == 0 and ((M // 64) * (N // 64) >= 256 or tiny)):
-        # shallow K (dH.W1, dQKV.W_in: K = ff, 3d) with enough 64x64 tiles to fill the chip: no
-        # split, C (+)= alpha acc straight from the epilogue -- no slabs, no reduce pass
-        K.gemm(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=trans_a, trans_b=trans_b, alpha=alpha,
-               epilogue=E.EPI_ACCUM if accumulate else E.EPI_STORE, precision=prec,
-               tile=256 if (M % 256 == 0 and N % 128 == 0 and (M // 256) * (N // 128) >= BIG_TILE_BLOCKS) else 64,
-               flops=flops, clamp_a=clamp_a, h3_exp=h3_exp)
+def _rules(dims: "Dims", prec: str, pd: float):
+    """role -> the executor's shape rules of this layer at that product's precision (native.layer_plan)."""
+    return lambda role: native.layer_plan(dims, _rp(role, prec), pd)
+
+
+def _gemm_split(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=False, alpha=1.0, accumulate=False, prec="fp32", rblk=None,
+                cblk=None, flops=None, deep=False, clamp_a=False, grouped=False, h3_exp=None):
+    """C (+)= alpha * op(A) . B with the executor's deterministic split-K (native.split_plan: tile, slab count and
+    the no-split exits).  Split: the depth goes into fp32 slabs and one streaming pass sums them into C -- applying
+    alpha, accumulation and an optional padded->real block map (rblk, cblk).  deep: a weight gradient; grouped: dQ /
+    dK, which the executor issues as one grouped launch; clamp_a: A is the signed probability image (read as Pd);
+    h3_exp: the f16x3 operand pre-scales (kernels.gemm)."""
+    sp = native.split_plan(M, N, Kd, prec, accumulate, deep, rblk is not None, grouped, _DEEP_WGRAD)
+    kw = dict(trans_a=trans_a, precision=prec, tile=sp.tile, flops=flops, clamp_a=clamp_a, h3_exp=h3_exp)
+    if sp.direct or (sp.split == 1 and rblk is None):   # one launch, C (+)= alpha acc straight from the epilogue
+        K.gemm(A, B, C, M, N, Kd, lda, ldb, ldc, alpha=alpha, epilogue=E.EPI_ACCUM if accumulate else E.EPI_STORE, **kw)
         return
-    if prec != "fp32" and M % 256 == 0 and N % 128 == 0 and (M // 256) * (N // 128) >= 32:
-        # 256x128 blocks (8 waves, one block per CU): the skinny attention products
-        t, tiles, target = 256, (M // 256) * (N // 128), target256
-    else:
-        t = 128 if (M % 128 == 0 and N % 128 == 0) else 64
-        tiles = (M // t) * (N // t)
-    split = max(1, min(target // max(tiles, 1), Kd // (4 * bk)))
-    if deep and _DEEP_WGRAD and prec != "fp32" and t == 128:
-        # weight gradients (a few dozen 128x128 output tiles, K = Np): the 16-deep K step runs 3
-        # blocks per CU; <= 16 slabs keeps the reduce pass short
-        t, split = 129, max(1, min(wgrad_split_cap(Kd), target // max(tiles, 1)))
-    mapped = rblk is not None
-    if split == 1 and not mapped:
-        K.gemm(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=trans_a, trans_b=trans_b, alpha=alpha,
-               epilogue=E.EPI_ACCUM if accumulate else E.EPI_STORE, precision=prec, tile=t, flops=flops,
-               clamp_a=clamp_a, h3_exp=h3_exp)
-        return
-    slabs = torch.empty(split, M, N, device=C.device, dtype=torch.float32)
-    K.gemm(A, B, slabs, M, N, Kd, lda, ldb, N, trans_a=trans_a, trans_b=trans_b, split_k=split, slab_stride=M * N,
-           precision=prec, tile=t, flops=flops, clamp_a=clamp_a, h3_exp=h3_exp)
-    K.slab_reduce(slabs, split, M * N, M, N, N, rblk or (M, M), cblk or (N, N), C, ldc, alpha=alpha,
+    slabs = torch.empty(sp.split, M, N, device=C.device, dtype=torch.float32)
+    K.gemm(A, B, slabs, M, N, Kd, lda, ldb, N, split_k=sp.split, slab_stride=M * N, **kw)
+    K.slab_reduce(slabs, sp.split, M * N, M, N, N, rblk or (M, M), cblk or (N, N), C, ldc, alpha=alpha,
                   accumulate=accumulate)
 
 
@@ -333,95 +289,46 @@ def _bias_grad(dY, rows, cols_pad, ld, cblk, out):
 def in_bias_grad(dQKV, Np, dp, d, out):
     """in_proj_bias gradient: column sums of dQKV's Q and V thirds; the K third is exactly zero (a softmax row
     is invariant to a constant added to its scores: sum_j dK_j = sum_i Q_i sum_j dS_ij = 0), written as the
-    column sum of zero rows.  Mirrors encoder_layer.cpp (same launches, same bits)."""
+    column sum of zero rows."""
     _bias_grad(dQKV, Np, dp, 3 * dp, (dp, d), out[:d])
     _bias_grad(dQKV[:, dp:], 0, dp, 3 * dp, (dp, d), out[d:2 * d])
     _bias_grad(dQKV[:, 2 * dp:], Np, dp, 3 * dp, (dp, d), out[2 * d:])
 
 
-def _gemm_nodes_k(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=False, alpha=1.0, prec="fp32", flops=None,
-                  clamp_a=False, grouped=False, h3_exp=None):
-    """The skinny attention products whose depth is the node dimension (N = dp, K = Np).  grouped: dQ / dK,
-    which the native executor issues as one grouped launch -- half the 256x128 block target each
-    (encoder_layer.cpp gemm_split), so both paths cut the same split-K slabs."""
-    _gemm_split(A, B, C, M, N, Kd, lda, ldb, ldc, trans_a=trans_a, alpha=alpha, prec=prec, flops=flops,
-                clamp_a=clamp_a, target256=120 if grouped else 240, h3_exp=h3_exp)
-
-
-def ffn2_split(dp: int, mfma: bool, Np: int, ffp: int) -> int:
-    """Split-K depth of FFN2 in the matrix-core precisions (encoder_layer.cpp ffn2_split), dp <= 256: with
-    fewer than 128 output tiles of 64x64, ~256 blocks of >= 4 K steps, finished by slab_bias_drop_resid_ln
-    (bias, dropout, residual and LayerNorm2)."""
-    tiles = (Np // 64) * (dp // 64)
-    if not mfma or dp > 256 or tiles >= 128:
-        return 1
-    return max(1, min(256 // tiles, ffp // 128))
-
-
-def qk_tile(Np: int) -> int:
-    """Tile of the S = Q K^T product (encoder_layer.cpp qk_tile): 256x128 blocks unless they would leave
-    most CUs idle (C5's Np = 2048: 128 blocks), then 128x128 (same per-element sums, same bits)."""
-    return 256 if Np % 256 == 0 and (Np // 256) * (Np // 128) >= 256 else 128
-
-
-SMALL_ATTN_MAX_D = 32
-
-
-def small_attn(d: int) -> bool:
-    """Node attention on the vector ALUs, flash-style (u2gnn_attn_small_*): feature widths d <= 32 in every
-    precision -- the matrix-core products would be >= 50 % padding (dp = 64) and the N x N images pure
-    overhead (encoder_layer.cpp small_attn applies the same rule)."""
-    return d <= SMALL_ATTN_MAX_D
-
-
-def mid_tail(d: int, dp: int, Np: int) -> bool:
-    """The forward tail (a3.3 + a3.4) of a mid-width layer with few rows as one row-block kernel + the slab
-    LayerNorm (u2gnn_layer_tail_mid_fwd; encoder_layer.cpp mid_tail applies the same rule)."""
-    return d > SMALL_ATTN_MAX_D and dp <= 256 and Np <= 512
-
-
-FUSED_MIN_NP = 1024   # encoder_layer.cpp kFusedMinNp
-
-
-def fused_attn(dp: int, prec_qk: str, prec_pv: str, Np: int = FUSED_MIN_NP) -> bool:
-    """Node-axis attention forward through the fused softmax.P.V kernel: Q K^T with the row-statistics epilogue
-    (bf16, bf16x3, bf16x6 or f16x3) and P.V in bf16 / bf16x3 / f16x3, dp <= 384, Np >= FUSED_MIN_NP
-    (encoder_layer.cpp fused_attn: fewer rows run the three-pass form; the fwd6 policy keeps the three-pass form,
-    the kernel's bf16x6 P.V is a tested capability, measured no faster)."""
-    return prec_qk != "fp32" and prec_pv in ("bf16", "bf16x3", "f16x3") and dp <= 384 and Np >= FUSED_MIN_NP
-
-
-def _attn_split(Q, Kt, V, N, Np, dp, pd, seeds, prec, att, dev):
+def _attn_split(Q, Kt, V, N, Np, dp, pd, seeds, prec, att, dev, rule):
     """a3.2 as three passes (fp32 parity path, dp > 384): S = Q K^T, softmax + dropout into the image,
     split-K P.V."""
     f32 = torch.float32
     S = torch.empty(Np, Np, device=dev, dtype=f32)
     K.gemm(Q, Kt, S, Np, Np, dp, 3 * dp, 3 * dp, Np, trans_b=True, precision=_rp("qk", prec), flops=att,
-           tile=256 if (_rp("qk", prec) != "fp32" and Np % 256 == 0) else 0)
+           tile=rule("qk").qk_tile_3pass)
     # one [Np, Np] image: with dropout the signed one (P/(1-p) where kept, -P where dropped), which
     # P.V and dP^T.dO read as Pd (negatives staged as 0) and the dS epilogue reads as P and keep
     Pd = torch.empty(Np, Np, device=dev, dtype=f32)
     K.attn_softmax_fwd(S, Np, None if pd > 0 else Pd, Pd, Np, N, Np, N, Np, pd, seeds.get(SITE_ATTN, 0))
     del S
     O = torch.empty(Np, dp, device=dev, dtype=f32)
-    _gemm_nodes_k(Pd, V, O, Np, dp, Np, Np, 3 * dp, dp, prec=_rp("pv", prec), flops=att, clamp_a=pd > 0,
-                  h3_exp=(K.h3_prob_exp(pd), K.H3_EXP) if _rp("pv", prec) == "f16x3" else None)
-    # (f16x3: the probability image's pre-scale, encoder_layer.cpp h3_prob_exp)
+    lp = rule("pv")   # (f16x3: the probability image has a pre-scale of its own)
+    _gemm_split(Pd, V, O, Np, dp, Np, Np, 3 * dp, dp, prec=_rp("pv", prec), flops=att, clamp_a=pd > 0,
+                h3_exp=(lp.h3_prob_exp, lp.h3_exp) if _rp("pv", prec) == "f16x3" else None)
     return Pd, O
 
 
 def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims: Dims, train: bool,
                           seeds: Dict[int, int], need_ctx: bool, prec: str = "fp32",
-                          p_drop: float = 0.5) -> (torch.Tensor, Optional[EncoderLayerCtx]):
+                          p_drop: float = 0.5, three_pass: bool = False) -> (torch.Tensor, Optional[EncoderLayerCtx]):
     """One torch TransformerEncoderLayer(d, nhead=1, ff, dropout=0.5) forward, post-LN, on the
-    slot-0 rows X [Np, dp] (pytorch_U2GNN_Sup.py:19-21,35)."""
+    slot-0 rows X [Np, dp] (pytorch_U2GNN_Sup.py:19-21,35).  three_pass: the attention forward as S = Q K^T,
+    softmax, P.V also where the executor runs the fused kernel (tools/prec_train_probe.py)."""
     N, Np, d, dp, ff, ffp = dims.N, dims.Np, dims.d, dims.dp, dims.ff, dims.ffp
     pd = p_drop if train else 0.0
     att = 2.0 * N * N * d          # algorithmic FLOPs of one attention product (real N, d)
     dev = X.device
     f32 = torch.float32
-    small = small_attn(d)
-    fused = not small and fused_attn(dp, _rp("qk", prec), _rp("pv", prec), Np)
+    rule = _rules(dims, prec, pd)
+    small = bool(rule("qk").small_attn)
+    # (precision experiments: an fp32 Q K^T has no row-statistics epilogue)
+    fused = bool(rule("pv").fused_attn) and _rp("qk", prec) != "fp32" and not three_pass
     QKV = QKV2 = None
     if not small:   # (the small-width attention projects into its own compact context)
         QKV = torch.empty(Np, 3 * dp, device=dev, dtype=f32)
@@ -430,22 +337,22 @@ def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims:
         QKV2 = torch.empty(Np, 6 * dp, device=dev, dtype=torch.bfloat16) if fused and _rp("pv", prec) != "bf16x6" else None
         K.gemm(X, w.W_in, QKV, Np, 3 * dp, dp, dp, dp, 3 * dp, trans_b=True, epilogue=E.EPI_BIAS, bias=w.b_in,
                alpha=1.0 / math.sqrt(d), scale_cols=dp, precision=_rp("in_proj", prec), flops=6.0 * N * d * d,
-               tile=256 if (_rp("in_proj", prec) != "fp32" and Np % 256 == 0 and (Np // 256) * (3 * dp // 128) >= BIG_TILE_BLOCKS) else 0,
+               tile=rule("in_proj").in_proj_tile,
                Cx2=QKV2, ldcx2=6 * dp, cx2_col0=2 * dp)
         Q, Kt, V = QKV[:, :dp], QKV[:, dp:2 * dp], QKV[:, 2 * dp:]
     if small:
-        # d <= 32: the whole layer on the vector ALUs (issued below with the tail: encoder_layer.cpp layer_fwd,
-        # launch for launch); the row statistics and a compact Q, K, V take the images' place in the context
+        # d <= 32: the whole layer on the vector ALUs (issued below with the tail); the row statistics and a
+        # compact Q, K, V take the images' place in the context
         O = torch.empty(Np, dp, device=dev, dtype=f32)
         Pd = torch.empty(K.attn_small_ctx_floats(Np, d), device=dev, dtype=f32)
     elif fused:
         # S = Q K^T written straight into the image buffer, with the softmax row partials of each 64-column
         # group from the GEMM epilogue; one fused softmax -> dropout -> P.V pass then overwrites S with the
-        # signed image and forms O (attn_fused.hip; encoder_layer.cpp layer_fwd, launch for launch)
+        # signed image and forms O (attn_fused.hip)
         Pd = torch.empty(Np, Np, device=dev, dtype=f32)
         rowpart = torch.empty(Np, 2 * (Np // 32), device=dev, dtype=f32)
         K.gemm(Q, Kt, Pd, Np, Np, dp, 3 * dp, 3 * dp, Np, trans_b=True, epilogue=E.EPI_STORE_ROWSTAT,
-               rowpart=rowpart, n_valid=N, precision=_rp("qk", prec), flops=att, tile=qk_tile(Np))
+               rowpart=rowpart, n_valid=N, precision=_rp("qk", prec), flops=att, tile=rule("qk").qk_tile)
         ws = torch.empty(K.attn_softmax_pv_ws_floats(N, Np, dp), device=dev, dtype=f32)
         O = torch.empty(Np, dp, device=dev, dtype=f32)
         x6 = _rp("pv", prec) == "bf16x6"
@@ -453,7 +360,7 @@ def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims:
                           ws, N, Np, pd, seeds.get(SITE_ATTN, 0), precision=_rp("pv", prec))
         del QKV2, rowpart, ws
     else:
-        Pd, O = _attn_split(Q, Kt, V, N, Np, dp, pd, seeds, prec, att, dev)
+        Pd, O = _attn_split(Q, Kt, V, N, Np, dp, pd, seeds, prec, att, dev, rule)
     Z1 = torch.empty(Np, dp, device=dev, dtype=f32)
     X1 = torch.empty(Np, dp, device=dev, dtype=f32)
     mean1 = torch.empty(Np, device=dev, dtype=f32)
@@ -464,15 +371,15 @@ def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims:
     mean2 = torch.empty(Np, device=dev, dtype=f32)
     rstd2 = torch.empty(Np, device=dev, dtype=f32)
     if small:
-        # in-projection, attention, a3.3 + a3.4 on the vector ALUs: 2 or 3 launches (encoder_layer.cpp layer_fwd)
+        # in-projection, attention, a3.3 + a3.4 on the vector ALUs: 2 or 3 launches
         K.layer_small_fwd(N, Np, d, dp, ff, ffp, pd, (seeds.get(SITE_DROP1, 0), seeds.get(SITE_DROPFF, 0),
                           seeds.get(SITE_DROP2, 0)), seeds.get(SITE_ATTN, 0), w.W_in, w.b_in, Pd, W_o=w.W_o,
                           b_o=w.b_o, n1_w=p.n1_w, n1_b=p.n1_b, W1=w.W1, b1=w.b1, W2=w.W2, b2=w.b2, n2_w=p.n2_w,
                           n2_b=p.n2_b, O=O, X=X, Z1=Z1, X1=X1, mean1=mean1, rstd1=rstd1, Hd=Hd, Z2=Z2, X2=X2,
                           mean2=mean2, rstd2=rstd2)
-    elif mid_tail(d, dp, Np):
+    elif rule("qk").mid_tail:
         # a3.3 + a3.4 in two launches: out-projection .. FFN2 partials per row block and hidden chunk, then the slab
-        # LayerNorm2 (mid_layer.hip; encoder_layer.cpp layer_fwd, launch for launch)
+        # LayerNorm2 (mid_layer.hip)
         ws = torch.empty(K.layer_tail_mid_ws_floats(Np, dp, ffp), device=dev, dtype=f32)
         K.layer_tail_mid_fwd(N, Np, d, dp, ff, ffp, pd, (seeds.get(SITE_DROP1, 0), seeds.get(SITE_DROPFF, 0),
                              seeds.get(SITE_DROP2, 0)), ws, W_o=w.W_o, b_o=w.b_o, n1_w=p.n1_w, n1_b=p.n1_b, W1=w.W1,
@@ -480,7 +387,7 @@ def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims:
                              rstd1=rstd1, Hd=Hd, Z2=Z2, X2=X2, mean2=mean2, rstd2=rstd2)
         del ws
     else:
-        fuse = fused_ln(dp, _rp("out_proj", prec))   # LayerNorm in the GEMM epilogue when a 64-column tile holds whole rows
+        fuse = bool(rule("out_proj").fused_ln)   # LayerNorm in the GEMM epilogue when a 64-column tile holds whole rows
         K.gemm(O, w.W_o, Z1, Np, dp, dp, dp, dp, dp, trans_b=True,
                epilogue=E.EPI_BIAS_DROP_RESID_LN if fuse else E.EPI_BIAS_DROP_RESID, bias=w.b_o,
                aux0=X, ld_aux=dp, p_drop=pd, seed=seeds.get(SITE_DROP1, 0), precision=_rp("out_proj", prec),
@@ -489,9 +396,8 @@ def encoder_layer_forward(X: torch.Tensor, w: PackedLayer, p: LayerParams, dims:
             K.layernorm_fwd(Z1, dp, p.n1_w, p.n1_b, X1, dp, mean1, rstd1, N, Np, d, dp)
         K.gemm(X1, w.W1, Hd, Np, ffp, dp, dp, dp, ffp, trans_b=True, epilogue=E.EPI_BIAS_RELU_DROP, bias=w.b1,
                p_drop=pd, seed=seeds.get(SITE_DROPFF, 0), precision=_rp("ffn1", prec), flops=2.0 * N * d * ff)
-        # (dp = 64: the out-projection's fused-LayerNorm rule decides, as in round 3)
-        f2 = ffn2_split(dp, fuse if dp == 64 else _rp("ffn2", prec) != "fp32", Np, ffp)
-        if f2 > 1:   # split-K slabs + the bias / dropout / residual / LayerNorm pass (encoder_layer.cpp layer_fwd)
+        f2 = rule("ffn2").ffn2_split
+        if f2 > 1:   # split-K slabs + the bias / dropout / residual / LayerNorm pass
             slabs = torch.empty(f2, Np, dp, device=dev, dtype=f32)
             K.gemm(Hd, w.W2, slabs, Np, dp, ffp, ffp, ffp, dp, trans_b=True, split_k=f2, slab_stride=Np * dp,
                    precision=_rp("ffn2", prec), flops=2.0 * N * d * ff, tile=64)
@@ -531,9 +437,11 @@ def encoder_layer_backward(dX2: torch.Tensor, ctx: EncoderLayerCtx, w: PackedLay
     if own:
         off = OffPath(dev)
     ws = torch.empty(K.colstat_ws_floats(N, dp), device=dev, dtype=f32)
-    use_ln_delta = ln_delta(_rp("ds", prec))
-    if small_attn(d):
-        # the row-local tail in one launch: dX1, dF, dH, dX, dA, dO and delta (encoder_layer.cpp layer_bwd); the
+    lp = native.layer_plan(dims, _rp("ds", prec), pd)
+    small = bool(lp.small_attn)
+    use_ln_delta = bool(lp.ln_delta)   # delta = rowsum(dO * O) from LayerNorm1's backward, else a rowdot launch
+    if small:
+        # the row-local tail in one launch: dX1, dF, dH, dX, dA, dO and delta; the
         # parameter gradients on the side stream in the matrix-core branch's order
         dX1, dF, dA, dO, dX = (torch.empty(Np, dp, device=dev, dtype=f32) for _ in range(5))
         dH = torch.empty(Np, ffp, device=dev, dtype=f32)
@@ -605,13 +513,13 @@ def encoder_layer_backward(dX2: torch.Tensor, ctx: EncoderLayerCtx, w: PackedLay
     if not use_ln_delta:
         delta = torch.empty(Np, device=dev, dtype=f32)
         K.rowdot(dO, dp, ctx.O, dp, delta, Np, dp)
-    if small_attn(d):
+    if small:
         # d <= 32: dQ, dK, dV (P recomputed from the saved context) and dX += dQKV W_in, run with the tail above
         dQKV = small_dqkv
         del dO
     else:
         dQKV = _attn_bwd_products(ctx, dO, delta, N, Np, d, dp, pd, att, prec, dev)
-    _in_proj_backward(dQKV, dX, ctx, w, g, N, Np, d, dp, prec, off, need_dx)
+    _in_proj_backward(dQKV, dX, ctx, w, g, N, Np, d, dp, prec, off, need_dx, small)
     if own:
         off.join()
     return dX if need_dx else None
@@ -626,20 +534,20 @@ def _attn_bwd_products(ctx, dO, delta, N, Np, d, dp, pd, att, prec, dev):
     K.gemm(dO, V, dS, Np, Np, dp, dp, 3 * dp, Np, trans_b=True, epilogue=E.EPI_ATTN_DS_SIGNED, aux0=ctx.Pd,
            p_drop=pd, rowvec=delta, ld_aux=Np, precision=_rp("ds", prec), flops=att)
     dQKV = torch.empty(Np, 3 * dp, device=dev, dtype=f32)
-    _gemm_nodes_k(ctx.Pd, dO, dQKV[:, 2 * dp:], Np, dp, Np, Np, dp, 3 * dp, trans_a=True, prec=_rp("dv", prec), flops=att,
-                  clamp_a=pd > 0)
-    _gemm_nodes_k(dS, Kt, dQKV[:, :dp], Np, dp, Np, Np, 3 * dp, 3 * dp, alpha=1.0 / math.sqrt(d), prec=_rp("dq", prec),
+    _gemm_split(ctx.Pd, dO, dQKV[:, 2 * dp:], Np, dp, Np, Np, dp, 3 * dp, trans_a=True, prec=_rp("dv", prec), flops=att,
+                clamp_a=pd > 0)
+    _gemm_split(dS, Kt, dQKV[:, :dp], Np, dp, Np, Np, 3 * dp, 3 * dp, alpha=1.0 / math.sqrt(d), prec=_rp("dq", prec),
                   flops=att, grouped=True)
-    _gemm_nodes_k(dS, Q, dQKV[:, dp:2 * dp], Np, dp, Np, Np, 3 * dp, 3 * dp, trans_a=True, prec=_rp("dk", prec), flops=att,
+    _gemm_split(dS, Q, dQKV[:, dp:2 * dp], Np, dp, Np, Np, 3 * dp, 3 * dp, trans_a=True, prec=_rp("dk", prec), flops=att,
                   grouped=True)
     del dS, dO
     return dQKV
 
 
-def _in_proj_backward(dQKV, dX, ctx, w, g, N, Np, d, dp, prec, off, need_dx):
+def _in_proj_backward(dQKV, dX, ctx, w, g, N, Np, d, dp, prec, off, need_dx, small):
     """dX += dQKV W_in (skipped when the input gradient is not wanted); the in-projection's weight and bias
     gradients (on the side stream unless this is the last layer of the backward)."""
-    if need_dx and not small_attn(d):   # (the small-width attention backward adds dQKV W_in itself)
+    if need_dx and not small:   # (the small-width attention backward adds dQKV W_in itself)
         _gemm_split(dQKV, w.W_in, dX, Np, dp, 3 * dp, 3 * dp, dp, dp, accumulate=True, prec=_rp("in_dx", prec),
                     flops=6.0 * N * d * d)
 

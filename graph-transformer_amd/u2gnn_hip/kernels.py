@@ -7,6 +7,7 @@ its status code.  Nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes
+import types
 
 import torch
 
@@ -73,18 +74,21 @@ def gemm_symbol(precision, M, N, split_k, tile, trans_a, trans_b, epilogue, clam
             f"{b(precision == 'bf16x3')}, {b(clamp_a)}>")   # the C++ template instance as rocprofv3 names it
 
 
-# f16x3 operand pre-scale exponents of the layer executor (encoder_layer.cpp kH3Exp / h3_prob_exp): activations
-# and weights (typical magnitudes 2^-5 .. 2^0) by 2^6; the probability image P (entries ~1/N, at most 1/(1-p)) by
-# 2^(15 - ceil(log2(1/(1-p)))), so that its largest entry stays below fp16's 65504 and its typical ones keep 22 bits
-H3_EXP = 6
+def _h3_plan(p_drop=0.0):
+    """The layer executor's f16x3 operand pre-scale exponents (u2gnn_layer_plan; they depend on p_drop alone)."""
+    from . import native
+    return native.layer_plan(types.SimpleNamespace(N=1, d=1, ff=1), "fp32", p_drop)
 
 
 def h3_prob_exp(p_drop):
-    e, m = 15, 1.0 / (1.0 - float(p_drop))
-    while m > 1.0:
-        m *= 0.5
-        e -= 1
-    return e
+    """Pre-scale exponent of the probability image at dropout p_drop."""
+    return _h3_plan(p_drop).h3_prob_exp
+
+
+def __getattr__(name):
+    if name == "H3_EXP":   # pre-scale exponent of activations and weights
+        return _h3_plan().h3_exp
+    raise AttributeError(name)
 
 
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, trans_a=False, trans_b=False, epilogue=_lib.EPI_STORE, split_k=1,
@@ -170,7 +174,7 @@ def _gemm_args(A, B, C, M, N, K, lda, ldb, ldc, trans_a=False, trans_b=False, ep
     if h3_exp is not None:
         a.h3_exp_a, a.h3_exp_b = int(h3_exp[0]), int(h3_exp[1])
     elif a.precision == _lib.PREC_F16X3:
-        a.h3_exp_a = a.h3_exp_b = H3_EXP
+        a.h3_exp_a = a.h3_exp_b = _h3_plan().h3_exp
     if ln is not None:
         gam, bet, Y, ldy, mean, rstd, d_real, rows, eps = ln
         _dev(gam, bet, Y, mean, rstd)
@@ -336,12 +340,9 @@ def layernorm_fwd(Z, ldz, gamma, beta, Y, ldy, mean, rstd, rows_valid, rows_pad,
           "u2gnn_layernorm_fwd")
 
 
-CS_ROWS = 16   # rows per partial chunk of the column reductions (encoder_ops.hip)
-
-
 def colstat_ws_floats(rows, cols):
     """Workspace of the two-pass column reductions (colsum, LN parameter gradients)."""
-    return max(1, (rows + CS_ROWS - 1) // CS_ROWS) * 3 * cols
+    return hip_lib().u2gnn_colstat_ws_floats(int(rows), int(cols))
 
 
 def layernorm_bwd(dY, ldy, Z, ldz, mean, rstd, gamma, dZ, lddz, dZdrop, lddrop, p, seed, rows_valid, rows_pad, d,

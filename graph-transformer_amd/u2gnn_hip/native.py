@@ -2,7 +2,9 @@
 include/u2gnn_hip.h u2gnn_layer_*): one C-ABI call per layer forward / backward.
 
 engine.py issues the same kernel sequence launch by launch from Python (kept as the readable
-reference orchestration and for per-GEMM event timing); this module is the production path.
+reference orchestration and for per-GEMM event timing); this module is the production path.  Every tile, split
+count and threshold of that sequence is decided in the executor alone: engine.py asks layer_plan / split_plan
+below (u2gnn_layer_plan, u2gnn_gemm_split_plan; host-only calls, cached by their arguments).
 Buffers come from the torch caching allocator: the forward's saved tensors live in one uint8
 "ctx" tensor per layer, workspaces are allocated per call.  Memory read by the backward's
 side stream is record_stream'ed so the allocator cannot recycle it early.
@@ -20,6 +22,10 @@ from ._lib import LayerDims, LayerGrads, LayerParamsC, LayerSeeds, check, hip_li
 from .kernels import PREC
 
 _SIZES: Dict[tuple, tuple] = {}
+_LAYER_PLANS: Dict[tuple, _lib.LayerPlan] = {}
+_SPLIT_PLANS: Dict[tuple, _lib.SplitPlan] = {}
+# a product precision that is no layer precision, as the layer precision whose forward products run on it
+_PRODUCT_PREC = {"bf16x6": "fwd6", "f16x3": "fwdh"}
 
 
 _ENABLED = [os.environ.get("U2GNN_NATIVE_LAYER", "1") == "1"]
@@ -64,6 +70,33 @@ def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = 
                                               ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
               "u2gnn_layer_sizes_csr")
         r = _SIZES[key] = (c.value, f.value, b.value)
+    return r
+
+
+def layer_plan(dims, prec: str, p_drop: float) -> _lib.LayerPlan:
+    """The executor's shape rules (u2gnn_layer_plan) of the node-axis layer dims (N, d, ff) at dropout p_drop; prec: a
+    layer precision, or the precision of the product the rule is asked for (engine._rp)."""
+    key = (dims.N, dims.d, dims.ff, prec, float(p_drop))
+    r = _LAYER_PLANS.get(key)
+    if r is None:
+        r = _lib.LayerPlan()
+        dd = _dims(dims.N, dims.d, dims.ff, _PRODUCT_PREC.get(prec, prec), True)
+        check(hip_lib().u2gnn_layer_plan(ctypes.byref(dd), float(p_drop), ctypes.byref(r)), "u2gnn_layer_plan")
+        _LAYER_PLANS[key] = r
+    return r
+
+
+def split_plan(M: int, N: int, K: int, prec: str, accumulate=False, deep=False, mapped=False, grouped=False,
+               deep_wgrad=True, held=False) -> _lib.SplitPlan:
+    """How the executor's split-K runs the product C[M, N] (+)= op(A) op(B) of depth K in the product precision
+    prec (u2gnn_gemm_split_plan; the flags: u2gnn_hip.h u2gnn_split_query)."""
+    key = (M, N, K, prec, accumulate, deep, mapped, grouped, deep_wgrad, held)
+    r = _SPLIT_PLANS.get(key)
+    if r is None:
+        r = _lib.SplitPlan()
+        q = _lib.SplitQuery(int(M), int(N), int(K), PREC[prec], *(int(bool(f)) for f in key[4:]))
+        check(hip_lib().u2gnn_gemm_split_plan(ctypes.byref(q), ctypes.byref(r)), "u2gnn_gemm_split_plan")
+        _SPLIT_PLANS[key] = r
     return r
 
 

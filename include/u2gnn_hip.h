@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define U2GNN_ABI_VERSION 18
+#define U2GNN_ABI_VERSION 19
 
 #define U2GNN_OK 0
 #define U2GNN_E_ARG (-1)    /* bad size / null pointer */
@@ -208,8 +208,10 @@ int u2gnn_pack_padded_multi_adv(const u2gnn_pack_desc *descs, int32_t n, uint64_
                                 void *stream);
 
 /* column sums (bias gradients):  out[map(c)] (+)= sum_{r<rows} X[r*ld + c], c < cols_pad.
- * ws must hold ceil(rows/16) * cols_pad floats (kernels.colstat_ws_floats allocates 3x that); 16-byte
+ * ws must hold ceil(rows/16) * cols_pad floats (u2gnn_colstat_ws_floats, ABI v19, gives 3x that: what
+ * u2gnn_layernorm_bwd_params takes for the same rows and columns; host-only); 16-byte
  * loads when X, ws are 16-byte aligned with ld and cols_pad multiples of 4, scalar loads otherwise. */
+int64_t u2gnn_colstat_ws_floats(int64_t rows, int64_t cols_pad);
 int u2gnn_colsum(const float *X, int64_t rows, int64_t cols_pad, int64_t ld, int64_t cblk_pad,
                  int64_t cblk_real, float *out, int32_t accumulate, float *ws, void *stream);
 
@@ -683,6 +685,48 @@ int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
                         int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream);
+
+/* ---- ABI v19: the executor's launch rules, for callers that issue the same kernels themselves (engine.py) ----
+ * Host-only, like u2gnn_layer_sizes: no HIP call, usable without a GPU.  u2gnn_layer_plan: the shape rules of the
+ * node-axis (or window) layer `dims` with dropout p_drop (0 <= p_drop < 1); dims as for u2gnn_layer_sizes.
+ * u2gnn_gemm_split_plan: how the executor's deterministic split-K runs one product C[M,N] (+)= op(A) op(B) of depth
+ * K (M, N multiples of 64, K of 16; the flags 0 / 1).  Bad arguments: U2GNN_E_ARG. */
+typedef struct u2gnn_layer_rules {
+    int64_t rows_pad, dp, ffp;   /* padded rows, model width, FFN width */
+    int64_t ffn2_split;          /* > 1: FFN2 as that many split-K slabs + u2gnn_slab_bias_drop_resid_ln */
+    int32_t small_attn;          /* the whole layer on the vector ALUs (u2gnn_layer_small_*) */
+    int32_t mid_tail;            /* the forward tail as u2gnn_layer_tail_mid_fwd */
+    int32_t fused_attn;          /* the attention forward as Q K^T with row statistics + u2gnn_attn_softmax_pv */
+    int32_t qk_tile;             /* tile of S = Q K^T in the fused attention forward ... */
+    int32_t qk_tile_3pass;       /* ... and in the three-pass form (0: the GEMM's own rule) */
+    int32_t in_proj_tile;        /* tile of the in-projection (0: the GEMM's own rule) */
+    int32_t fused_ln;            /* LayerNorm inside the bias-dropout-residual GEMM epilogues */
+    int32_t ln_delta;            /* delta = rowsum(dO * O) from LayerNorm1's backward (else u2gnn_rowdot) */
+    int32_t h3_exp;              /* f16x3 pre-scale exponent of activations and weights ... */
+    int32_t h3_prob_exp;         /* ... and of the probability image at p_drop */
+    int32_t reserved[6];
+} u2gnn_layer_rules;
+int u2gnn_layer_plan(const u2gnn_layer_dims *dims, float p_drop, u2gnn_layer_rules *plan);
+typedef struct u2gnn_split_query {
+    int64_t M, N, K;
+    int32_t precision;    /* U2GNN_PREC_* of the product */
+    int32_t accumulate;   /* C += the product */
+    int32_t deep;         /* a weight gradient (K = the rows) */
+    int32_t mapped;       /* the result goes through a padded -> real block map */
+    int32_t grouped;      /* one of two products that share a grouped launch (dQ, dK) */
+    int32_t deep_wgrad;   /* the layer's U2GNN_LAYER_DEEP_WGRAD */
+    int32_t held;         /* held back to its layer's grouped launch */
+    int32_t reserved[5];
+} u2gnn_split_query;
+typedef struct u2gnn_split_plan {
+    int32_t direct;        /* one launch straight into C, no slabs (shallow K or tiny): tile 64 or 256, split 1 */
+    int32_t tile;          /* the rule's tile: 64, 128, 129 (128x128 on the 16-deep K step) or 256 (256x128) */
+    int32_t launch_tile;   /* what the executor launches: 128 lowered to 64 for a held-back or < 64-block product
+                              (the same k-ordered sums) */
+    int32_t split;         /* split-K slabs (1: none) */
+    int32_t reserved[4];
+} u2gnn_split_plan;
+int u2gnn_gemm_split_plan(const u2gnn_split_query *query, u2gnn_split_plan *plan);
 
 /* ---- ABI v5: live launch timing of one product of the layer executor (diagnostics) ----
  * u2gnn_probe_arm(role, capacity) creates `capacity` pairs of timing events; every following

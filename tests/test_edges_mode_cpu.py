@@ -92,13 +92,13 @@ def test_transpose_round_trips_and_bad_csrs_are_refused():
             Adjacency.from_csr(bad_rp, bad_ci, n, device="cpu")
 
 
-def test_library_exports_csr_entry_points_under_abi_18():
+def test_library_exports_csr_entry_points():
     from u2gnn_hip import _lib
     lib = _lib.hip_lib()
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name), name
         assert name in _lib.header_symbols("u2gnn_hip.h"), name
-    assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 18
+    assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 19
 
 
 def _layer_args(window=0):

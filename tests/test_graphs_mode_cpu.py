@@ -12,14 +12,14 @@ PKG = os.path.join(REPO, "graph-transformer_amd")
 E_ARG = -1
 
 
-def test_library_exports_segment_entry_points_under_abi_18():
+def test_library_exports_segment_entry_points():
     from u2gnn_hip import _lib
     lib = _lib.hip_lib()
     for name in ("u2gnn_segment_attn_fwd", "u2gnn_segment_attn_bwd", "u2gnn_layer_sizes_seg", "u2gnn_layer_fwd_seg",
                  "u2gnn_layer_bwd_seg"):
         assert hasattr(lib, name), name
         assert name in _lib.header_symbols("u2gnn_hip.h"), name
-    assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 18
+    assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 19
 
 
 def _layer_args(window=0):

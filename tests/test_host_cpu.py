@@ -23,7 +23,7 @@ def test_libraries_export_every_header_symbol(header, loader):
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
     if loader == "hip_lib":
-        assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 18
+        assert lib.u2gnn_abi_version() == _lib.ABI_VERSION == 19
 
 
 def test_kernel_wrappers_refuse_host_tensors():
@@ -261,22 +261,117 @@ def test_layer_executor_refuses_undersized_buffers_before_launching():
     assert rc == -1
 
 
+def _layer_plan(N, d, ff, prec="bf16x3", p_drop=0.5):
+    """u2gnn_layer_plan of the node-axis layer, straight from the library (no cache in between)."""
+    import ctypes
+    from u2gnn_hip import _lib, native
+    plan = _lib.LayerPlan()
+    dims = native._dims(N, d, ff, prec, True)
+    assert _lib.hip_lib().u2gnn_layer_plan(ctypes.byref(dims), p_drop, ctypes.byref(plan)) == 0
+    return plan
+
+
 def test_round5_shape_rules():
-    """The Python orchestration's copies of the executor's round-5 shape rules (encoder_layer.cpp mid_tail,
-    ffn2_split; engine.py mirrors them launch for launch) at the bench configurations, and the mid tail's
-    workspace sizing (a host-only entry point)."""
-    from u2gnn_hip import engine as E
+    """The executor's round-5 shape rules (encoder_layer.cpp mid_tail, ffn2_split, read through u2gnn_layer_plan:
+    what the Python orchestration launches by) at the bench configurations, and the mid tail's workspace sizing
+    (a host-only entry point)."""
     from u2gnn_hip import kernels as K
-    assert E.mid_tail(136, 192, 128) and E.mid_tail(100, 128, 128) and E.mid_tail(40, 64, 512)   # C2-class
-    assert not E.mid_tail(32, 64, 128)        # d <= 32: the small-width layer
-    assert not E.mid_tail(367, 384, 4864)     # C4: the matrix-core path
-    assert not E.mid_tail(136, 192, 640)      # more than 512 padded rows
-    assert E.ffn2_split(128, True, 128, 1024) == 8     # C2: 4 output tiles -> 8 slabs of 4 K steps
-    assert E.ffn2_split(384, True, 4864, 1024) == 1    # C4: 456 tiles fill the chip
-    assert E.ffn2_split(64, True, 2048, 1024) == 8     # a d <= 64 layer at 2048 rows (the round-3 rule)
-    assert E.ffn2_split(128, False, 128, 1024) == 1    # fp32 parity path: no split
-    assert E.ffn2_split(320, True, 128, 1024) == 1     # dp > 256: no slab LayerNorm
+
+    def mid_tail(N, d):
+        return bool(_layer_plan(N, d, 1024).mid_tail)
+
+    def ffn2_split(N, d, prec):
+        return _layer_plan(N, d, 1024, prec).ffn2_split
+    assert mid_tail(100, 136) and mid_tail(100, 100) and mid_tail(500, 40)   # C2-class: (dp, Np) = (192, 128) ...
+    assert not mid_tail(100, 32)         # d <= 32: the small-width layer
+    assert not mid_tail(4700, 367)       # C4: the matrix-core path
+    assert not mid_tail(640, 136)        # more than 512 padded rows
+    assert ffn2_split(100, 128, "bf16x3") == 8     # C2: 4 output tiles -> 8 slabs of 4 K steps
+    assert ffn2_split(4700, 384, "bf16x3") == 1    # C4: 456 tiles fill the chip
+    assert ffn2_split(2048, 64, "bf16x3") == 8     # a d <= 64 layer at 2048 rows (the round-3 rule)
+    assert ffn2_split(100, 128, "fp32") == 1       # fp32 parity path: no split
+    assert ffn2_split(100, 320, "bf16x3") == 1     # dp > 256: no slab LayerNorm
     assert K.layer_tail_mid_ws_floats(128, 128, 1024) == 8 * 128 * 128
     assert K.layer_tail_mid_ws_floats(128, 192, 256) == 2 * 128 * 192   # ff = 200 padded to 256: 2 chunks
     assert K.layer_tail_mid_ws_floats(128, 192, 200) == -1              # unpadded widths are refused
     assert K.layer_tail_mid_ws_floats(128, 320, 1024) == -1
+
+
+# (N, d, ff) of the bench configurations: C2 (IMDBBINARY), C3 (PTC), C4 (COLLAB) over nodes and over its 17
+# neighbour-token rows per node, C5 (REDDIT-M5K)
+_BENCH_DIMS = {"c2": (100, 136, 1024), "c3": (100, 19, 1024), "c4": (4700, 367, 1024), "c4_tokens": (79900, 367, 1024),
+               "c5": (1914, 4, 1024)}
+_PLAN_FIELDS = ("rows_pad", "dp", "ffp", "small_attn", "mid_tail", "fused_attn", "qk_tile", "qk_tile_3pass",
+                "in_proj_tile", "fused_ln", "ffn2_split", "ln_delta", "h3_exp", "h3_prob_exp")
+# the values engine.py's own rule functions gave before it read them from the library (p_drop 0.5)
+_PINNED_LAYER_PLANS = {
+    ("c2", "fp32"): (128, 192, 1024, 0, 1, 0, 128, 0, 0, 0, 1, 0, 6, 14),
+    ("c2", "bf16x3"): (128, 192, 1024, 0, 1, 0, 128, 0, 0, 0, 8, 1, 6, 14),
+    ("c3", "fp32"): (128, 64, 1024, 1, 0, 0, 128, 0, 0, 0, 1, 0, 6, 14),
+    ("c3", "bf16x3"): (128, 64, 1024, 1, 0, 0, 128, 0, 0, 1, 8, 1, 6, 14),
+    ("c4", "fp32"): (4864, 384, 1024, 0, 0, 0, 256, 0, 0, 0, 1, 0, 6, 14),
+    ("c4", "bf16x3"): (4864, 384, 1024, 0, 0, 1, 256, 256, 0, 0, 1, 1, 6, 14),
+    ("c4_tokens", "fp32"): (80128, 384, 1024, 0, 0, 0, 256, 0, 0, 0, 1, 0, 6, 14),
+    ("c4_tokens", "bf16x3"): (80128, 384, 1024, 0, 0, 1, 256, 256, 256, 0, 1, 1, 6, 14),
+    ("c5", "fp32"): (2048, 64, 1024, 1, 0, 0, 128, 0, 0, 0, 1, 0, 6, 14),
+    ("c5", "bf16x3"): (2048, 64, 1024, 1, 0, 0, 128, 256, 0, 1, 8, 1, 6, 14),
+}
+# (M, N, K, precision, accumulate, deep, mapped, grouped, deep_wgrad, held) -> (direct, tile, launch_tile, split).
+# tile and split: what engine._gemm_split launched before it read them from the library (direct: its shallow-K
+# exit); launch_tile: 128 lowered to 64 for a held-back or < 64-block bf16 product, else the tile.
+_PINNED_SPLIT_PLANS = {
+    # the C4 backward (Np 4864, dp 384, ffp 1024): dV, dQ, dK, the four weight gradients, dH W1, dQKV W_in
+    (4864, 384, 4864, "bf16x3", 0, 0, 0, 0, 1, 0): (0, 256, 256, 4),
+    (4864, 384, 4864, "bf16x3", 0, 0, 0, 1, 1, 0): (0, 256, 256, 2),    # grouped: half the 240-block target
+    (384, 1024, 4864, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 129, 129, 8),
+    (1024, 384, 4864, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 129, 129, 8),
+    (384, 384, 4864, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 129, 129, 8),     # deep 129 at the cap of 8 slabs
+    (1152, 384, 4864, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 129, 129, 8),
+    (4864, 384, 1024, "bf16x3", 1, 0, 0, 0, 1, 0): (1, 64, 64, 1),
+    (4864, 384, 1152, "bf16x3", 1, 0, 0, 0, 1, 0): (1, 64, 64, 1),
+    (4864, 384, 4864, "fp32", 0, 0, 0, 1, 1, 0): (0, 128, 128, 3),
+    (384, 384, 4864, "fp32", 0, 1, 1, 0, 1, 0): (0, 128, 128, 49),
+    # the C5 backward (Np 2048, dp 64, ffp 1024)
+    (2048, 64, 2048, "bf16x3", 0, 0, 0, 0, 1, 0): (0, 64, 64, 14),
+    (2048, 64, 2048, "bf16x3", 0, 0, 0, 1, 1, 0): (0, 64, 64, 14),
+    (64, 1024, 2048, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 64, 64, 16),
+    (1024, 64, 2048, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 64, 64, 16),
+    (64, 64, 2048, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 64, 64, 16),
+    (192, 64, 2048, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 64, 64, 16),
+    (2048, 64, 1024, "bf16x3", 1, 0, 0, 0, 1, 0): (0, 64, 64, 8),
+    (2048, 64, 192, "bf16x3", 1, 0, 0, 0, 1, 0): (0, 64, 64, 1),
+    # one case per exit
+    (128, 128, 384, "bf16x3", 1, 0, 0, 0, 1, 0): (1, 64, 64, 1),        # tiny: one short accumulating launch
+    (80128, 384, 1152, "bf16x3", 1, 0, 0, 0, 1, 0): (1, 256, 256, 1),   # shallow K with >= 768 blocks of 256x128
+    (384, 384, 80128, "bf16x3", 0, 1, 1, 0, 1, 0): (0, 129, 129, 16),   # deep 129 at the token-depth cap of 16
+    (384, 384, 4864, "bf16x3", 0, 1, 1, 0, 0, 0): (0, 128, 128, 38),    # without the layer's DEEP_WGRAD flag
+    (384, 384, 4864, "bf16x3", 0, 1, 1, 0, 0, 1): (0, 128, 64, 38),     # ... held back: 64x64 in the grouped launch
+    (128, 128, 1024, "bf16x3", 1, 0, 0, 0, 1, 0): (0, 128, 64, 8),      # 8 blocks of 128x128: launched as 64x64
+    (128, 128, 1024, "fp32", 1, 0, 0, 0, 1, 0): (0, 128, 128, 16),      # (never lowered in fp32)
+}
+
+
+def test_executor_plans_are_pinned():
+    """u2gnn_layer_plan / u2gnn_gemm_split_plan give, at the bench configurations and at one case per exit of the
+    split-K rule, the tiles, splits and thresholds the step was measured and held bit-equal with; engine.row_pad is
+    the plan's rows_pad; bad queries are refused."""
+    import ctypes
+    from u2gnn_hip import _lib, native
+    from u2gnn_hip.engine import row_pad
+    for (cfg, prec), want in _PINNED_LAYER_PLANS.items():
+        plan = _layer_plan(*_BENCH_DIMS[cfg], prec)
+        assert tuple(getattr(plan, f) for f in _PLAN_FIELDS) == want, (cfg, prec)
+    assert _layer_plan(100, 136, 1024, "fwdh", 0.0).h3_prob_exp == 15 and _layer_plan(1, 1, 1, "fp32", 0.9).h3_prob_exp == 11
+    for q, want in _PINNED_SPLIT_PLANS.items():
+        sp = native.split_plan(*q)
+        assert (sp.direct, sp.tile, sp.launch_tile, sp.split) == want, q
+    for N in range(1, 5001):
+        assert _layer_plan(N, 4, 64, "fp32", 0.0).rows_pad == row_pad(N), N
+    lib, plan, sp = _lib.hip_lib(), _lib.LayerPlan(), _lib.SplitPlan()
+    for bad in (_lib.LayerDims(0, 4, 64, 0, 0, 0, 0), _lib.LayerDims(10, 1025, 64, 0, 0, 0, 0), _lib.LayerDims(10, 4, 64, 3, 0, 0, 0)):
+        assert lib.u2gnn_layer_plan(ctypes.byref(bad), 0.0, ctypes.byref(plan)) == -1
+    assert lib.u2gnn_layer_plan(ctypes.byref(_lib.LayerDims(10, 4, 64, 0, 0, 0, 0)), 1.0, ctypes.byref(plan)) == -1
+    assert lib.u2gnn_layer_plan(None, 0.0, ctypes.byref(plan)) == -1
+    for bad in ((100, 64, 64, 1), (64, 64, 24, 1), (64, 64, 64, 5), (0, 64, 64, 1)):   # M, K not padded; precision
+        assert lib.u2gnn_gemm_split_plan(ctypes.byref(_lib.SplitQuery(*bad)), ctypes.byref(sp)) == -1
+    assert lib.u2gnn_gemm_split_plan(ctypes.byref(_lib.SplitQuery(64, 64, 64, 1, 2)), ctypes.byref(sp)) == -1   # a flag of 2

@@ -30,7 +30,7 @@ POLICIES = {   # name -> (layer precision, role overrides)
     "x6_all": ("bf16x3", {r: "bf16x6" for r in FWD}),
     "fwd6": ("fwd6", {}),
     "fwdh": ("fwdh", {}),
-    "fwdh_3pass": ("fwdh", {}),   # the three-pass attention forward (engine.FUSED_MIN_NP raised for this policy)
+    "fwdh_3pass": ("fwdh", {}),   # the three-pass attention forward (EncoderStack.three_pass)
     "fwd32": ("fwd32", {}),
     "x6_nopv": ("bf16x3", {r: "bf16x6" for r in ("in_proj", "qk", "out_proj", "ffn1", "ffn2")}),
     "x6_noqk": ("bf16x3", {r: "bf16x6" for r in ("in_proj", "pv", "out_proj", "ffn1", "ffn2")}),
@@ -61,7 +61,6 @@ def main():
         if a == "--policies":
             only = sys.argv[i + 1].split(",")
     native.set_enabled(False)
-    fused_min_np = engine.FUSED_MIN_NP
     dev = "cuda"
     torch.set_num_threads(min(16, os.cpu_count()))
     np.random.seed(123)
@@ -149,10 +148,10 @@ def main():
                 continue
             engine.ROLE_PREC.clear()
             engine.ROLE_PREC.update(roles)
-            engine.FUSED_MIN_NP = 1 << 30 if pname.endswith("_3pass") else fused_min_np
             m = TransformerU2GNN(d, ff, C, T, 0.5, L, precision=base)
             m.load_state_dict(sd0)
             m = m.to(dev).train()
+            m.core.stack.three_pass = pname.endswith("_3pass")
             flat = m.flatten_parameters()
             scores, ctx = m.core.forward(b, train=True, need_ctx=True, seed=seed)
             dsc = torch.empty_like(scores)
