@@ -49,6 +49,10 @@ struct Dims {
     // null while planning: the sizes depend on csr_nnz only)
     const u2gnn_csr_attn *csr = nullptr;
     int64_t csr_nnz = 0;
+    // its per-entry additive bias (u2gnn_layer_*_csrb): csr_nnz device floats, and where the backward leaves dL/dbias;
+    // both caller-owned, null: none
+    const float *csr_bias = nullptr;
+    float *csr_dbias = nullptr;
 };
 
 // attention over a row pattern (segments or a CSR): the generic route with a statistics-saving fp32 attention kernel
@@ -56,11 +60,12 @@ bool sparse_attn(const Dims &D) { return D.n_seg || D.csr_nnz; }
 
 // The attention pattern of a call (n_seg row segments, a CSR of nnz entries, or neither: the node-axis or window
 // layer).  Segments: offsets and count, both or neither.  CSR: none, or a complete one with at least one entry.  Never
-// the two together, and neither with window mode.  The planning form (u2gnn_layer_sizes_*) has counts only and no
+// the two together, and neither with window mode.  A bias only with a CSR, its gradient only with the bias.  The planning form (u2gnn_layer_sizes_*) has counts only and no
 // pointers.
 bool pattern_ok(const Dims &D, bool plan) {
     const bool segs = D.seg || D.n_seg, csr = D.csr || D.csr_nnz;
     if (D.n_seg < 0 || D.csr_nnz < 0 || (segs && csr) || ((segs || csr) && D.window != 0)) return false;
+    if ((D.csr_bias && !csr) || (D.csr_dbias && !D.csr_bias)) return false;
     if (plan) return true;
     if (segs && !(D.seg && D.n_seg >= 1)) return false;
     const u2gnn_csr_attn *A = D.csr;
@@ -609,8 +614,8 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     } else if (D.csr_nnz) {
         // neighbour attention: every row over the columns of its CSR row (csr_attn.hip), exact fp32
         if (!plan)
-            U2GNN_TRY(u2gnn_csr_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.csr, c.O, dp, c.stats, pd, s->attn, N, Np,
-                                         st));
+            U2GNN_TRY(u2gnn_csr_attn_fwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.csr, D.csr_bias, c.O, dp, c.stats, pd,
+                                              s->attn, N, Np, st));
     } else if (small_attn(D)) {
         // d <= 32: the whole layer on the vector ALUs (small_layer.hip): in-projection, softmax -> dropout -> P.V
         // flash-style (the row statistics and a compact Q, K, V saved) and a3.3 + a3.4 -- 2 or 3 launches
@@ -831,8 +836,8 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         dQKV = W.take<float>(Np * 3 * dp);
         float *edge_ws = W.take<float>(2 * D.csr_nnz);
         if (!plan)
-            U2GNN_TRY(u2gnn_csr_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.csr, c.O, dO, dp, c.stats, pd, s->attn, q_scale,
-                                         dQKV, 3 * dp, edge_ws, N, Np, st));
+            U2GNN_TRY(u2gnn_csr_attn_bwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.csr, D.csr_bias, c.O, dO, dp, c.stats, pd,
+                                              s->attn, q_scale, dQKV, 3 * dp, edge_ws, D.csr_dbias, N, Np, st));
     } else if (small_attn(D)) {
         // d <= 32: dQ, dK, dV (P recomputed from the row statistics) and dX += dQKV W_in, run with the tail above
         dQKV = small_dqkv;
@@ -939,15 +944,23 @@ int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_b
     return u2gnn_layer_sizes_seg(dims, p_drop, 0, ctx_bytes, fwd_ws_bytes, bwd_ws_bytes);
 }
 
-int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
-                        const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, void *stream) {
+int u2gnn_layer_fwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                         const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, const float *bias,
+                         void *stream) {
     if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    D.csr_bias = bias;
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     return plan_then_run(ctx, ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
         return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
     });
+}
+
+int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                        const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, void *stream) {
+    return u2gnn_layer_fwd_csrb(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, seg_offsets, n_seg, A, nullptr, stream);
 }
 
 int u2gnn_layer_fwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
@@ -962,18 +975,28 @@ int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, c
     return u2gnn_layer_fwd_seg(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, nullptr, 0, stream);
 }
 
-int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
-                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
-                        int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream) {
+int u2gnn_layer_bwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                         int32_t n_seg, const u2gnn_csr_attn *A, const float *bias, float *dbias, void *stream,
+                         void *side_stream) {
     if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
+    D.csr_bias = bias, D.csr_dbias = dbias;
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     // (planned with this call's schedule: its streams and whether dX is wanted)
     return plan_then_run(const_cast<void *>(ctx), ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
         return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
                          reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
     });
+}
+
+int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                        const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                        const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                        int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream) {
+    return u2gnn_layer_bwd_csrb(dims, w, s, X, ctx, ctx_bytes, dX2, dX, g, ws, ws_bytes, seg_offsets, n_seg, A, nullptr,
+                                nullptr, stream, side_stream);
 }
 
 int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,

@@ -52,10 +52,13 @@ struct W16 {
     __device__ __forceinline__ void load(const float *W, int64_t ldw, int i0, int valid_, int klim_, int lane) {
         valid = valid_, klim = klim_;
         const int il = valid_ > 0 ? valid_ - 1 : 0, kl = klim_ > 0 ? klim_ - 1 : 0;
+        // a batch with no valid row (a wave beyond the dp / 16 or nu / 16 batches, whose prefetch is unconditional)
+        // starts past the matrix: it reads row 0 instead
+        const int ib = valid_ > 0 ? i0 : 0;
 #pragma unroll
         for (int i = 0; i < 16; ++i)
 #pragma unroll
-            for (int m = 0; m < CPLK; ++m) v[i][m] = W[(int64_t)(i0 + min(i, il)) * ldw + min(lane + 64 * m, kl)];
+            for (int m = 0; m < CPLK; ++m) v[i][m] = W[(int64_t)(ib + min(i, il)) * ldw + min(lane + 64 * m, kl)];
     }
 };
 

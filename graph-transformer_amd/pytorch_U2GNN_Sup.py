@@ -21,13 +21,18 @@ so a graph's scores do not depend on the other graphs of the batch; it needs eac
 consecutive rows, which ``forward`` checks on its graph_pool) or "edges" (a node attends over itself and its
 graph neighbours: the batch's adjacency plus the diagonal, ``DeviceBatch.adj`` =
 ``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``; structure-aware without sampling and, as "graphs",
-independent of the batch; reference-style tensor inputs carry no edges, so ``forward`` raises a ValueError for them).
+independent of the batch; reference-style tensor inputs carry no edges, so ``forward`` raises a ValueError for them);
+``hops`` = None, or H in [1, 31] with attention="edges": a node attends over every node of its graph within H bonds
+(``Adjacency.from_csr(rowptr, colidx, N, device, etype=etype)`` of ``store.adjacency(graph_ids, hops=H)``) and each
+encoder layer adds a learned scalar per shortest-path distance to its scores: ONE more parameter, ``hop_bias``
+[L, T, H + 1], zero-initialised and registered after every other, so the rest of the model keeps its values under a
+seed and, without ``hops``, the state_dict keys are the reference's.
 """
 import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, FlatParams, SupCore
+from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, FlatParams, SupCore, check_hops, hop_bias_last
 
 
 class _SupFunction(torch.autograd.Function):
@@ -49,7 +54,7 @@ class _SupFunction(torch.autograd.Function):
 class TransformerU2GNN(nn.Module):
 
     def __init__(self, feature_dim_size, ff_hidden_size, num_classes,
-                 num_self_att_layers, dropout, num_U2GNN_layers, precision="fp32", attention="nodes"):
+                 num_self_att_layers, dropout, num_U2GNN_layers, precision="fp32", attention="nodes", hops=None):
         super(TransformerU2GNN, self).__init__()
         self.feature_dim_size = feature_dim_size
         self.ff_hidden_size = ff_hidden_size
@@ -61,6 +66,7 @@ class TransformerU2GNN(nn.Module):
         if attention not in ATTENTION_MODES:
             raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
+        self.hops = check_hops(hops, attention)
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()
         for _ in range(self.num_U2GNN_layers):
@@ -73,7 +79,13 @@ class TransformerU2GNN(nn.Module):
         for _ in range(self.num_U2GNN_layers):
             self.predictions.append(nn.Linear(self.feature_dim_size, self.num_classes))
             self.dropouts.append(nn.Dropout(dropout))
+        if self.hops:   # after every reference parameter; zeros: torch's generator is not touched
+            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers, self.hops + 1))
         self._core = None
+
+    def named_parameters(self, prefix='', recurse=True, remove_duplicate=True):
+        """torch's, with hop_bias (registered last, but a parameter of the model itself) listed last."""
+        return hop_bias_last(super().named_parameters(prefix, recurse, remove_duplicate), prefix)
 
     @property
     def core(self) -> SupCore:

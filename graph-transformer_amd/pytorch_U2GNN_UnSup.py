@@ -17,7 +17,9 @@ Extra keyword ``attention``: "nodes" (the fork: attention over all nodes of the 
 each node over its k+1 sampled neighbours) or "graphs" (each node over the nodes of its own graph; the batch must
 be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`` / ``from_store`` build them) or
 "edges" (each node over itself and its graph neighbours; the batch must be a ``DeviceBatch`` whose ``adj`` is
-``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``, else a ValueError).
+``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``, else a ValueError).  ``hops`` = None, or H in [1, 31]
+with attention="edges": attention over the H-hop neighbourhood with a learned bias per shortest-path distance, one more
+trainable parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last), as in pytorch_U2GNN_Sup.
 """
 import math
 
@@ -27,7 +29,7 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from sampled_softmax import SampledSoftmax
 from u2gnn_hip import kernels as K
-from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch
+from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, check_hops, hop_bias_last
 from u2gnn_hip.engine import site_seed
 from u2gnn_hip.unsup import SITE_SS_DROP, UnSupCore
 
@@ -68,7 +70,8 @@ class TransformerU2GNN(nn.Module):
 
     def __init__(self, vocab_size, feature_dim_size, ff_hidden_size, sampled_num,
                  num_self_att_layers, num_U2GNN_layers, dropout, device, sampler_type='default',
-                 loss_type='default', adj_mat=None, single_layer_only=True, precision="fp32", attention="nodes"):
+                 loss_type='default', adj_mat=None, single_layer_only=True, precision="fp32", attention="nodes",
+                 hops=None):
         super(TransformerU2GNN, self).__init__()
         if sampler_type != 'default' or loss_type != 'default':
             raise NotImplementedError("only sampler_type='default', loss_type='default' (graph-level U2GNN) "
@@ -77,6 +80,7 @@ class TransformerU2GNN(nn.Module):
         if attention not in ATTENTION_MODES:
             raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
+        self.hops = check_hops(hops, attention)
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size
         self.num_self_att_layers = num_self_att_layers
@@ -100,11 +104,17 @@ class TransformerU2GNN(nn.Module):
         self.ss = SampledSoftmax(self.vocab_size, self.sampled_num, self.feature_dim_size * self.num_U2GNN_layers,
                                  self.device)
         self.reset_parameters()
+        if self.hops:   # after every other parameter; zeros: torch's generator is not touched
+            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers, self.hops + 1))
         self._core = None
 
     def reset_parameters(self):
         stdv = math.sqrt(6.0 / (self.weight.size(0) + self.weight.size(1)))
         self.weight.data.uniform_(-stdv, stdv)
+
+    def named_parameters(self, prefix='', recurse=True, remove_duplicate=True):
+        """torch's, with hop_bias (registered last, but a parameter of the model itself) listed last."""
+        return hop_bias_last(super().named_parameters(prefix, recurse, remove_duplicate), prefix)
 
     @property
     def core(self) -> UnSupCore:
@@ -113,8 +123,9 @@ class TransformerU2GNN(nn.Module):
         return self._core
 
     def trainable_names(self):
-        """Parameters on the loss path (encoders + ss.weight)."""
-        return [n for n, _ in self.named_parameters() if n.startswith("u2gnn_layers.") or n == "ss.weight"]
+        """Parameters on the loss path (encoders + ss.weight, and hop_bias with ``hops``)."""
+        return [n for n, _ in self.named_parameters()
+                if n.startswith("u2gnn_layers.") or n in ("ss.weight", "hop_bias")]
 
     def forward(self, X_concat, input_x, input_y, args=None):
         if isinstance(X_concat, DeviceBatch):
@@ -126,7 +137,7 @@ class TransformerU2GNN(nn.Module):
             b = DeviceBatch(N, 1, input_x.contiguous(), X_concat.to(torch.float32).contiguous(), None, None, None,
                             None, input_y)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.training else 0
-        names = [n for n in self.trainable_names() if n.startswith("u2gnn_layers.")]
+        names = [n for n in self.trainable_names() if n != "ss.weight"]
         params = [dict(self.named_parameters())[n] for n in names]
         if torch.is_grad_enabled():
             OV = _EncodeFn.apply(self.core, b, self.training, seed, names, *params)

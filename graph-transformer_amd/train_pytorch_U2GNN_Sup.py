@@ -10,7 +10,7 @@ Execution: the default trainer is the fused HIP step (u2gnn_hip.train.SupTrainer
 backward into a flat grad buffer, device-side clip + Adam, no per-step host sync except the loss
 readout the reference also does).  ``--autograd`` runs the reference's exact loop instead
 (model(), cross_entropy, loss.backward(), clip_grad_norm_, torch Adam, StepLR) — on the same kernels.
-Extra flags: --precision, --attention, --autograd, --max_steps (0 = full epochs), --world_size /
+Extra flags: --precision, --attention, --hops, --autograd, --max_steps (0 = full epochs), --world_size /
 --dist_backend (data parallelism, u2gnn_hip.cli: one process per GPU, a global step = world_size
 consecutive batches of the single stream with the averaged gradient, RCCL all-reduce under the backward).
 """
@@ -55,6 +55,10 @@ parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors
                          "each node attends over itself and its graph neighbours (the batch's adjacency, which "
                          "the modes {nodes, neighbors, graphs} do not read; no sampling, and a graph's output "
                          "does not depend on its batch either)")
+parser.add_argument("--hops", default=0, type=int,
+                    help="with --attention edges: each node attends over every node of its graph within this many "
+                         "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
+                         "scores (one more parameter, hop_bias); 0 = off, the plain adjacency")
 parser.add_argument("--autograd", action="store_true", help="reference loop: autograd + torch Adam/StepLR")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
@@ -64,6 +68,10 @@ parser.add_argument("--world_size", default=1, type=int,
 parser.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend: nccl = RCCL over xGMI; gloo = several ranks on one GPU (tests)")
 args = parser.parse_args()
+if args.hops and args.attention != "edges":
+    parser.error("--hops needs --attention edges")
+if not 0 <= args.hops <= 31:
+    parser.error("--hops must be in 0..31")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -104,7 +112,7 @@ log("Loading data... finished!")
 model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.ff_hidden_size,
                          num_classes=num_classes, dropout=args.dropout, num_self_att_layers=args.num_timesteps,
                          num_U2GNN_layers=args.num_hidden_layers, precision=args.precision,
-                         attention=args.attention).to(device)
+                         attention=args.attention, hops=args.hops or None).to(device)
 num_batches_per_epoch = int((len(train_graphs) - 1) / args.batch_size) + 1
 # global steps per epoch: each consumes world_size batches of the stream
 steps_per_epoch = -(-num_batches_per_epoch // run.world)
@@ -118,7 +126,10 @@ def to_device(hb, store=train_store):
         b = DeviceBatch.from_store(hb, train_X, device=device)
     else:
         b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
-    if args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
+    if args.hops:                     # the H-hop lists and each entry's distance (hop_bias's index)
+        rowptr, colidx, etype = store.adjacency(hb.graph_ids, hops=args.hops)
+        b.adj = Adjacency.from_csr(rowptr, colidx, b.N, device=device, etype=etype)
+    elif args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
         b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
     return b
 

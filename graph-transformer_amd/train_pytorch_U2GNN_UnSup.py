@@ -9,7 +9,7 @@ LogisticRegression(liblinear, tol=1e-3) (:164-188), stdout line (:207) and acc f
 (<run_folder>/../runs_pytorch_U2GNN_UnSup/<model_name>/checkpoints/model_acc.txt).
 
 The fork's file cannot run as shipped; this runs its working semantics
-(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --max_steps,
+(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --hops, --max_steps,
 --world_size / --dist_backend (data parallelism, u2gnn_hip.cli: rank r trains batch r of each global step
 with the r-th sample draw of the step; encoder gradients all-reduced, the touched ss.weight rows
 all-gathered, dp.UnSupGradSync).
@@ -55,6 +55,11 @@ parser.add_argument("--attention", default="nodes", choices=["nodes", "neighbors
                          "the modes {nodes, neighbors, graphs} do not read; no sampling, and a graph's output "
                          "does not depend on its batch either)")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
+parser.add_argument("--hops", default=0, type=int,
+                    help="with --attention edges: each node attends over every node of its graph within this many "
+                         "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
+                         "scores (one more parameter, hop_bias); 0 = off, the plain adjacency.  Not with --world_size "
+                         "> 1: the unsupervised gradient exchange does not carry hop_bias yet")
 parser.add_argument("--world_size", default=1, type=int,
                     help="data-parallel ranks, one per GPU (started here under torch.distributed.run unless a "
                          "launcher already set WORLD_SIZE; left at 1 under a launcher it takes WORLD_SIZE).  "
@@ -62,6 +67,12 @@ parser.add_argument("--world_size", default=1, type=int,
 parser.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend: nccl = RCCL over xGMI; gloo = several ranks on one GPU (tests)")
 args = parser.parse_args()
+if args.hops and args.attention != "edges":
+    parser.error("--hops needs --attention edges")
+if not 0 <= args.hops <= 31:
+    parser.error("--hops must be in 0..31")
+if args.hops and (args.world_size > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+    parser.error("--hops is not available with --world_size > 1 in the unsupervised trainer")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -105,7 +116,7 @@ model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.
                          dropout=args.dropout, num_self_att_layers=args.num_timesteps,
                          vocab_size=vocab_size, sampled_num=args.sampled_num,
                          num_U2GNN_layers=args.num_hidden_layers, device=device, precision=args.precision,
-                         attention=args.attention).to(device)
+                         attention=args.attention, hops=args.hops or None).to(device)
 trainer = UnSupTrainer(model, lr=args.learning_rate, max_norm=0.5)
 if run.world > 1:
     broadcast_params(trainer.flat)
@@ -129,7 +140,10 @@ def train():
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
         b = DeviceBatch.from_store(hb, store_X, device=device)
-        if args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
+        if args.hops:                     # the H-hop lists and each entry's distance (hop_bias's index)
+            rowptr, colidx, etype = store.adjacency(hb.graph_ids, hops=args.hops)
+            b.adj = Adjacency.from_csr(rowptr, colidx, b.N, device=device, etype=etype)
+        elif args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
             b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]

@@ -32,6 +32,7 @@ EPI_STORE, EPI_BIAS, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU_DROP, EPI_RELU_DROP_BWD,
     EPI_ATTN_DS_SIGNED, EPI_ATTN_DS_RECOMP, EPI_BIAS_DROP_RESID_LN, EPI_STORE_ROWDOT, EPI_STORE_ROWSTAT = range(12)
 ABI_VERSION = 19   # include/u2gnn_hip.h U2GNN_ABI_VERSION
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4
+BIAS_TYPES_MAX = 32   # U2GNN_BIAS_TYPES_MAX: entry types (hop distances) of an attention bias table
 
 
 class GemmArgs(ctypes.Structure):
@@ -185,6 +186,16 @@ _HIP_SIGS = {
     "u2gnn_csr_attn_fwd": ([VP, I64, I32, POINTER(CsrAttn), VP, I64, VP, F32, c_uint64, I64, I64, VP], c_int32),
     "u2gnn_csr_attn_bwd": ([VP, I64, I32, POINTER(CsrAttn), VP, VP, I64, VP, F32, c_uint64, F32, VP, I64, VP, I64, I64,
                             VP], c_int32),
+    "u2gnn_csr_attn_fwd_bias": ([VP, I64, I32, POINTER(CsrAttn), VP, VP, I64, VP, F32, c_uint64, I64, I64, VP], c_int32),
+    "u2gnn_csr_attn_bwd_bias": ([VP, I64, I32, POINTER(CsrAttn), VP, VP, VP, I64, VP, F32, c_uint64, F32, VP, I64, VP,
+                                 VP, I64, I64, VP], c_int32),
+    "u2gnn_bias_expand": ([VP, I32, I32, VP, I64, VP, I64, VP], c_int32),
+    "u2gnn_bias_table_grad_ws_floats": ([I32, I32, I64], I64),
+    "u2gnn_bias_table_grad": ([VP, I64, I32, I32, VP, I64, VP, VP, I64, VP], c_int32),
+    "u2gnn_layer_fwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
+                              VP, I32, POINTER(CsrAttn), VP, VP], c_int32),
+    "u2gnn_layer_bwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,
+                              POINTER(LayerGrads), VP, I64, VP, I32, POINTER(CsrAttn), VP, VP, VP, VP], c_int32),
     "u2gnn_layer_sizes_csr": ([POINTER(LayerDims), F32, I32, I64, POINTER(c_int64), POINTER(c_int64),
                                POINTER(c_int64)], c_int32),
     "u2gnn_layer_fwd_csr": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,

@@ -52,6 +52,55 @@ def csr_with_self(N: int, rows: np.ndarray, cols: np.ndarray):
     return rowptr, np.ascontiguousarray(keys % max(N, 1))
 
 
+def hop_lists(n: int, deg: np.ndarray, start: np.ndarray, nbr: np.ndarray, hops: int):
+    """One graph's ``hops``-hop lists in its local numbering: (counts int32 [n], cols int32 [nnz], dist uint8 [nnz]) --
+    row i lists every node within shortest-path distance <= hops of i (itself at distance 0), columns ascending.
+    Node i's neighbours are nbr[start[i] .. start[i] + deg[i]) (local ids; repeats are harmless).  A breadth-first
+    sweep from all sources at once over (source, node) pairs: the frontier of distance h is every neighbour of the
+    frontier of h - 1 that no earlier frontier reached.  numpy only."""
+    n1 = max(n, 1)
+    seen = np.arange(n, dtype=np.int64) * (n + 1)                  # keys source * n + node, sorted: the diagonal
+    keys, dist = [seen], [np.zeros(n, dtype=np.uint8)]
+    frontier = seen
+    for h in range(1, hops + 1):
+        src, node = frontier // n1, frontier % n1
+        d = deg[node]
+        total = int(d.sum())
+        if total == 0:
+            break
+        pos = np.repeat(start[node] - (np.cumsum(d) - d), d) + np.arange(total, dtype=np.int64)
+        frontier = np.setdiff1d(np.repeat(src, d) * n + nbr[pos], seen)
+        if frontier.size == 0:
+            break
+        seen = np.union1d(seen, frontier)
+        keys.append(frontier)
+        dist.append(np.full(frontier.size, h, dtype=np.uint8))
+    keys, dist = np.concatenate(keys), np.concatenate(dist)
+    order = np.argsort(keys, kind="stable")
+    keys = keys[order]
+    return np.bincount(keys // n1, minlength=n).astype(np.int32), (keys % n1).astype(np.int32), dist[order]
+
+
+def batch_hop_lists(lists, sizes: np.ndarray):
+    """(rowptr int64 [N+1], colidx int64 [nnz], etype int32 [nnz]) of a batch from its graphs' ``hop_lists`` (in batch
+    order) and node counts: the lists concatenated, the columns moved to the batch's row numbering."""
+    offsets = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    rowptr = np.zeros(int(offsets[-1]) + 1, dtype=np.int64)
+    if not lists:
+        return rowptr, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    np.cumsum(np.concatenate([c for c, _, _ in lists]), out=rowptr[1:])
+    per_graph = np.array([len(c) for _, c, _ in lists], dtype=np.int64)
+    colidx = np.concatenate([c for _, c, _ in lists]).astype(np.int64) + np.repeat(offsets[:-1], per_graph)
+    return rowptr, colidx, np.concatenate([d for _, _, d in lists]).astype(np.int32)
+
+
+def check_hops_range(hops) -> int:
+    if int(hops) != hops or not 1 <= int(hops) <= 31:
+        raise ValueError(f"adjacency: hops must be an integer in [1, 31], got {hops!r}")
+    return int(hops)
+
+
 class GraphStore:
     """Per-dataset arrays: node features, labels, neighbour CSR in the reference's order."""
 
@@ -88,11 +137,30 @@ class GraphStore:
     def degrees_of(self, ids) -> np.ndarray:
         return np.concatenate([self.deg[self.node_start[i]:self.node_start[i + 1]] for i in ids])
 
-    def adjacency(self, graph_ids: Sequence[int]):
+    def _hop_lists(self, gi: int, hops: int):
+        """Graph ``gi``'s lists (``hop_lists``), computed on first use and kept in the store."""
+        cache = self.__dict__.setdefault("_hop_cache", {}).setdefault(hops, {})
+        hit = cache.get(gi)
+        if hit is None:
+            n, lo = int(self.n_nodes[gi]), int(self.node_start[gi])
+            hit = cache[gi] = hop_lists(n, self.deg[lo:lo + n], self.nbr_start[lo:lo + n], self.nbr, hops)
+        return hit
+
+    def adjacency(self, graph_ids: Sequence[int], hops: Optional[int] = None):
         """(rowptr [N+1], colidx [nnz]), int64, of the batch ``graph_ids`` in the batch's row numbering (graph
         ``graph_ids[g]`` = rows offsets[g] .. offsets[g+1]-1, as ``assemble`` lays them out): row i lists itself and
         its graph neighbours, sorted and without repeats -- what attention="edges" attends over
-        (``core.Adjacency.from_csr``).  Deterministic: nothing is drawn from any RNG."""
+        (``core.Adjacency.from_csr``).  Deterministic: nothing is drawn from any RNG.
+
+        hops = H (1 <= H <= 31): (rowptr, colidx, etype) instead -- row i lists every node of its graph within
+        shortest-path distance <= H, itself included (unreachable nodes never), sorted and without repeats, and
+        etype[e] (int32) is that distance, 0 on the diagonal.  H = 1 gives the rowptr / colidx above.  A graph's
+        lists do not depend on the batch: they are computed on first use and kept in the store (``_hop_lists``), a
+        batch concatenates them."""
+        if hops is not None:
+            hops = check_hops_range(hops)
+            ids = np.asarray(graph_ids, dtype=np.int64)
+            return batch_hop_lists([self._hop_lists(int(g), hops) for g in ids], self.n_nodes[ids])
         ids = np.asarray(graph_ids, dtype=np.int64)
         sizes = self.n_nodes[ids]
         offsets = np.zeros(len(ids) + 1, dtype=np.int64)

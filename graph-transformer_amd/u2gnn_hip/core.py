@@ -18,6 +18,7 @@ import torch
 
 from . import kernels as K
 from . import native
+from ._lib import BIAS_TYPES_MAX
 from .engine import deep_wgrad as engine_deep_wgrad
 from .engine import (SITE_ATTN, SITE_DROP1, SITE_DROP2, SITE_DROPFF, SITE_HEAD, Dims, LayerParams, PackedLayer,
                      OffPath, encoder_layer_backward, encoder_layer_forward, rup, side_stream_pays, site_seed)
@@ -50,19 +51,23 @@ class Adjacency:
     """The attention pattern of attention="edges" on the device: row i attends over colidx[rowptr[i] .. rowptr[i+1])
     (GraphStore.adjacency: the node itself and its graph neighbours), with the transpose the backward walks: for
     column j the entries e = t_eid[t] (indices into colidx) and their rows t_src[t], t in t_rowptr[j] ..
-    t_rowptr[j+1].  Five int64 tensors and nnz; the kernels never hand them back to the host."""
-    __slots__ = ("N", "nnz", "rowptr", "colidx", "t_rowptr", "t_src", "t_eid", "_c")
+    t_rowptr[j+1].  Five int64 tensors and nnz; the kernels never hand them back to the host.  With ``hops``
+    (GraphStore.adjacency(ids, hops=H)) also etype, int32 [nnz]: the shortest-path distance of each entry, the index
+    into the model's hop_bias tables, and n_types = max(etype) + 1."""
+    __slots__ = ("N", "nnz", "rowptr", "colidx", "t_rowptr", "t_src", "t_eid", "etype", "n_types", "_c")
 
-    def __init__(self, N, rowptr, colidx, t_rowptr, t_src, t_eid):
+    def __init__(self, N, rowptr, colidx, t_rowptr, t_src, t_eid, etype=None, n_types=0):
         self.N, self.nnz = int(N), int(colidx.numel())
         self.rowptr, self.colidx, self.t_rowptr, self.t_src, self.t_eid = rowptr, colidx, t_rowptr, t_src, t_eid
+        self.etype, self.n_types = etype, int(n_types)
         self._c = None
 
     @staticmethod
-    def from_csr(rowptr, colidx, N: int, device="cuda") -> "Adjacency":
+    def from_csr(rowptr, colidx, N: int, device="cuda", etype=None) -> "Adjacency":
         """Validates the CSR on the host (ValueError: rowptr not [N+1], not starting at 0, decreasing or not ending
-        at len(colidx); a column outside [0, N)), builds the transpose by a stable argsort of the columns (the
-        entries of a column keep their row order) and moves the five arrays to ``device``."""
+        at len(colidx); a column outside [0, N); etype not one value per entry or outside [0, 32)), builds the
+        transpose by a stable argsort of the columns (the entries of a column keep their row order) and moves the
+        five arrays (and etype, as int32) to ``device``."""
         rp = np.ascontiguousarray(np.asarray(rowptr), dtype=np.int64).reshape(-1)
         ci = np.ascontiguousarray(np.asarray(colidx), dtype=np.int64).reshape(-1)
         N = int(N)
@@ -72,13 +77,22 @@ class Adjacency:
             raise ValueError("adjacency: rowptr must start at 0, never decrease and end at len(colidx)")
         if ci.shape[0] and (ci.min() < 0 or ci.max() >= N):
             raise ValueError(f"adjacency: a column index outside [0, {N})")
+        et, n_types = None, 0
+        if etype is not None:
+            et = np.ascontiguousarray(np.asarray(etype), dtype=np.int64).reshape(-1)
+            if et.shape[0] != ci.shape[0]:
+                raise ValueError(f"adjacency: etype must hold one value per entry ({ci.shape[0]}), got {et.shape[0]}")
+            if et.shape[0] and (et.min() < 0 or et.max() >= BIAS_TYPES_MAX):
+                raise ValueError(f"adjacency: an entry type outside [0, {BIAS_TYPES_MAX})")
+            n_types = int(et.max()) + 1 if et.shape[0] else 0
         order = np.argsort(ci, kind="stable")                       # entry ids grouped by column, rows ascending
         t_rowptr = np.zeros(N + 1, dtype=np.int64)
         np.cumsum(np.bincount(ci, minlength=N), out=t_rowptr[1:])
         rows = np.repeat(np.arange(N, dtype=np.int64), np.diff(rp))
         dev = torch.device(device)
         h2d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)  # noqa: E731
-        return Adjacency(N, h2d(rp), h2d(ci), h2d(t_rowptr), h2d(rows[order]), h2d(order))
+        et_dev = None if et is None else torch.from_numpy(et.astype(np.int32)).to(dev)
+        return Adjacency(N, h2d(rp), h2d(ci), h2d(t_rowptr), h2d(rows[order]), h2d(order), et_dev, n_types)
 
     def c_struct(self):
         """The u2gnn_csr_attn of these arrays (kept alive with them)."""
@@ -232,16 +246,45 @@ def _check_range_host(input_x, N: int):
 ATTENTION_MODES = ("nodes", "neighbors", "graphs", "edges")
 
 
+def hop_bias_last(named, prefix: str = ""):
+    """A model's named_parameters() with ``hop_bias`` moved to the end.  torch lists a module's own parameters before
+    its children's, which would put hop_bias first; last, every other parameter keeps its place in the flat buffer
+    (FlatParams) and the region after the last encoder layer ends where hop_bias begins (dp.OverlappedGradAllReduce)."""
+    key = (prefix + "." if prefix else "") + "hop_bias"
+    held = None
+    for n, p in named:
+        if n == key:
+            held = (n, p)
+        else:
+            yield n, p
+    if held is not None:
+        yield held
+
+
+def check_hops(hops, attention: str) -> Optional[int]:
+    """The ``hops`` keyword of the models: None (off) or an H in [1, 31], and only with attention="edges"."""
+    if hops is None:
+        return None
+    if attention != "edges":
+        raise ValueError(f"hops needs attention='edges', got attention={attention!r}")
+    if int(hops) != hops or not 1 <= int(hops) <= BIAS_TYPES_MAX - 1:
+        raise ValueError(f"hops must be an integer in [1, {BIAS_TYPES_MAX - 1}], got {hops!r}")
+    return int(hops)
+
+
 class EncoderStack:
     """L U2GNN layers x T post-LN encoder layers on slot-0 rows, with the re-gather between
     U2GNN layers (pytorch_U2GNN_Sup.py:33-39; pytorch_U2GNN_UnSup.py:55-64)."""
 
     def __init__(self, u2gnn_layers, d: int, ff: int, T: int, L: int, prec: str = "fp32", p_enc: float = 0.5,
-                 attention: str = "nodes"):
+                 attention: str = "nodes", hops: Optional[int] = None, hop_bias=None):
+        """hops = H with attention="edges": every layer adds hop_bias()[l][t][distance] to its attention scores;
+        hop_bias: a callable that returns the model's [L, T, H + 1] parameter (read where it lies at each forward)."""
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
         if attention not in ATTENTION_MODES:
             raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
         self.attention = attention
+        self.hops, self.hop_bias = check_hops(hops, attention), hop_bias
         self.packed = None
         # Python orchestration only: the three-pass attention forward where the fused kernel would run
         # (tools/prec_train_probe.py)
@@ -289,6 +332,18 @@ class EncoderStack:
             if b.adj.N != b.N:
                 raise ValueError(f"attention='edges': the adjacency is over {b.adj.N} rows, the batch has {b.N}")
             adjacency = b.adj
+        # hops: the per-entry bias of all L * T layers, expanded from the tables in one launch.  The tables are read
+        # where the parameter lies (the flat buffer under a trainer), so a replayed HIP graph sees Adam's updates
+        bias_all = None
+        if self.hops:
+            if adjacency.etype is None:
+                raise ValueError("hops needs the entries' distances: Adjacency.from_csr(rowptr, colidx, N, device, "
+                                 "etype=etype) with (rowptr, colidx, etype) = store.adjacency(graph_ids, hops=H)")
+            if adjacency.n_types > self.hops + 1:
+                raise ValueError(f"hops={self.hops}: the adjacency holds distances up to {adjacency.n_types - 1}")
+            tables = self.hop_bias().detach().view(self.L * self.T, self.hops + 1)
+            bias_all = torch.empty(self.L * self.T, rup(adjacency.nnz, 4), device=tables.device, dtype=torch.float32)
+            K.bias_expand(tables, adjacency.etype, bias_all)
         dev = b.X_concat.device
         d, dp = self.d, rup(self.d, 64)
         dims = Dims(b.N, d, self.ff)
@@ -304,7 +359,9 @@ class EncoderStack:
                 if native.enabled():
                     X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                 need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(),
-                                                segments=segments, adjacency=adjacency)
+                                                segments=segments, adjacency=adjacency,
+                                                bias=None if bias_all is None else
+                                                bias_all[l * self.T + t, :adjacency.nnz])
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                  need_ctx, self.prec, self.p_enc, three_pass=self.three_pass)
@@ -401,6 +458,10 @@ class EncoderStack:
         dims = ctx["dims"]
         dnext = None
         off = OffPath(b.input_x.device, enabled=side_stream_pays(dims))
+        # hops: every layer leaves dL/dbias of its entries in its row; one reduction to the tables after the last layer
+        dbias_all = None
+        if self.hops:
+            dbias_all = torch.empty(self.L * self.T, rup(b.adj.nnz, 4), device=b.input_x.device, dtype=torch.float32)
         for l in reversed(range(self.L)):
             dX = ext_grad(l)
             if dnext is not None:
@@ -414,12 +475,16 @@ class EncoderStack:
                 if isinstance(lc, native.NativeCtx):
                     dX = native.layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, dims,
                                                self.prec, side=off.side, deep_wgrad=engine_deep_wgrad(),
-                                               need_dx=need_dx)
+                                               need_dx=need_dx,
+                                               dbias=None if dbias_all is None else
+                                               dbias_all[l * self.T + t, :b.adj.nnz])
                 else:
                     dX = encoder_layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, dims,
                                                 self.prec, off=off, need_dx=need_dx)
                 self._layer_grads_done(pre, off, need_dx)
             dnext = dX
+        if dbias_all is not None:
+            K.bias_table_grad(dbias_all, b.adj.etype, grads["hop_bias"].view(self.L * self.T, self.hops + 1))
         off.join()   # parameter gradients complete before the caller's optimizer reads them
         return dnext
 
@@ -438,7 +503,8 @@ class SupCore:
         self.p_head = module.dropout_p        # args.dropout, pytorch_U2GNN_Sup.py:28
         # encoder dropout is hard-coded to 0.5 (pytorch_U2GNN_Sup.py:20)
         self.stack = EncoderStack(module.u2gnn_layers, self.d, self.ff, self.T, self.L, precision, 0.5,
-                                  getattr(module, "attention", "nodes"))
+                                  getattr(module, "attention", "nodes"), getattr(module, "hops", None),
+                                  lambda: module.hop_bias)
 
     def forward(self, b: DeviceBatch, train: bool, need_ctx: bool, seed: int):
         dev = b.X_concat.device

@@ -115,7 +115,12 @@ class OverlappedGradAllReduce:
                   for n in flat.names if n.startswith(layer_prefix) and ".layers." in n}
         self.n_layers = len(layers)
         enc_hi = max((b for n, (a, b) in self.span.items() if n.startswith(layer_prefix)), default=0)
-        self.tail = (self._align_end(enc_hi), flat.gflat.numel())   # [head parameters, end)
+        # [head parameters, end): what is complete before the encoder backward starts.  hop_bias (the last parameter of
+        # a model with hops) is not: its gradient is reduced from all layers after the last one's backward, so the
+        # tail ends where it begins and its region goes out with the leftovers in __call__, on the step's stream
+        # after that reduction
+        tail_hi = self.span["hop_bias"][0] if "hop_bias" in self.span else flat.gflat.numel()
+        self.tail = (self._align_end(enc_hi), max(tail_hi, self._align_end(enc_hi)))
         self.acc: Optional[Tuple[int, int]] = None
         self.acc_stream = None
         self.calls = 0

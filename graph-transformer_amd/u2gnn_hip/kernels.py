@@ -327,6 +327,67 @@ def csr_attn_bwd(QKV, dp, adjacency, O, dO, stats, p, seed, q_scale, dQKV, N, ro
                                        int(rows_pad), _s()), "u2gnn_csr_attn_bwd")
 
 
+def _entry_bias(t, nnz, what):
+    """A per-entry bias / bias gradient of a CSR: at least nnz contiguous float32 on the device."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < int(nnz):
+        raise _lib.U2GNNNativeError(f"{what}: a contiguous float32 device tensor of nnz = {int(nnz)} entries")
+
+
+def csr_attn_fwd_bias(QKV, dp, adjacency, bias, O, stats, p, seed, N, rows_pad):
+    """csr_attn_fwd with the score of entry e = Qs_i . K_col(e) + bias[e]; bias: nnz floats in colidx order."""
+    _dev(QKV, bias, O, stats)
+    _entry_bias(bias, adjacency.nnz, "bias")
+    check(hip_lib().u2gnn_csr_attn_fwd_bias(_p(QKV), QKV.stride(0), int(dp), _csr(adjacency, QKV), _p(bias), _p(O),
+                                            O.stride(0), _p(stats), float(p), int(seed), int(N), int(rows_pad), _s()),
+          "u2gnn_csr_attn_fwd_bias")
+
+
+def csr_attn_bwd_bias(QKV, dp, adjacency, bias, O, dO, stats, p, seed, q_scale, dQKV, dbias, N, rows_pad):
+    """csr_attn_bwd under the forward's bias; dbias (nnz floats, or None) receives dL/dbias[e] = dS_e."""
+    _dev(QKV, bias, O, dO, stats, dQKV, dbias)
+    _entry_bias(bias, adjacency.nnz, "bias")
+    if dbias is not None:
+        _entry_bias(dbias, adjacency.nnz, "dbias")
+    if O.stride(0) != dO.stride(0):
+        raise _lib.U2GNNNativeError("O and dO share one leading dimension")
+    A = _csr(adjacency, QKV)
+    ws = torch.empty(2 * max(1, int(adjacency.nnz)), device=QKV.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_csr_attn_bwd_bias(_p(QKV), QKV.stride(0), int(dp), A, _p(bias), _p(O), _p(dO), dO.stride(0),
+                                            _p(stats), float(p), int(seed), float(q_scale), _p(dQKV), dQKV.stride(0),
+                                            _p(ws), _p(dbias), int(N), int(rows_pad), _s()),
+          "u2gnn_csr_attn_bwd_bias")
+
+
+def bias_expand(tables, etype, out):
+    """out[r][e] = tables[r][etype[e]]: tables f32 [R, n_types] (any contiguous view, read where it lies), etype int32
+    [nnz], out f32 [R, ld >= nnz] (its first nnz columns are written); a type outside [0, n_types) gives 0."""
+    _dev(tables, etype, out)
+    if etype.dtype != torch.int32 or not etype.is_contiguous() or not tables.is_contiguous() or out.stride(1) != 1:
+        raise _lib.U2GNNNativeError("bias_expand: contiguous tables, int32 etype, row-major out")
+    R, n_types = tables.shape
+    if out.shape[0] != R or out.shape[1] < etype.numel():
+        raise _lib.U2GNNNativeError("bias_expand: out holds one row of at least nnz columns per table")
+    check(hip_lib().u2gnn_bias_expand(_p(tables), int(R), int(n_types), _p(etype), etype.numel(), _p(out),
+                                      out.stride(0) if R > 1 else out.shape[1], _s()), "u2gnn_bias_expand")
+
+
+def bias_table_grad(dbias, etype, dtables):
+    """dtables[r][t] = sum of dbias[r][e] over the entries with etype[e] == t: dbias f32 [R, ld] (ld % 4 == 0, its
+    first nnz = len(etype) columns are read), dtables f32 [R, n_types] contiguous, overwritten.  Deterministic."""
+    _dev(dbias, etype, dtables)
+    if etype.dtype != torch.int32 or not etype.is_contiguous() or not dtables.is_contiguous() or dbias.stride(1) != 1:
+        raise _lib.U2GNNNativeError("bias_table_grad: row-major dbias, int32 etype, contiguous dtables")
+    R, n_types = dtables.shape
+    if dbias.shape[0] != R or dbias.shape[1] < etype.numel():
+        raise _lib.U2GNNNativeError("bias_table_grad: dbias holds one row of at least nnz columns per table")
+    nnz = etype.numel()
+    n = hip_lib().u2gnn_bias_table_grad_ws_floats(int(R), int(n_types), int(nnz))
+    ws = torch.empty(max(1, n), device=dbias.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_bias_table_grad(_p(dbias), dbias.stride(0) if R > 1 else dbias.shape[1], int(R), int(n_types),
+                                          _p(etype), int(nnz), _p(dtables), _p(ws), ws.numel(), _s()),
+          "u2gnn_bias_table_grad")
+
+
 def rowdot(A, lda, B, ldb, out, rows, cols):
     _dev(A, B, out)
     check(hip_lib().u2gnn_rowdot(_p(A), int(lda), _p(B), int(ldb), _p(out), int(rows), int(cols), _s()),

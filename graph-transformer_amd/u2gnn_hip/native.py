@@ -114,7 +114,7 @@ def _seeds(p_drop: float, seeds: Dict[int, int]) -> LayerSeeds:
 
 class NativeCtx:
     """What the backward needs from one layer's forward."""
-    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments", "adjacency")
+    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments", "adjacency", "bias")
 
 
 def _adjacency(adjacency, dev):
@@ -138,22 +138,37 @@ def _stream(s=None):
     return ctypes.c_void_p((s or torch.cuda.current_stream()).cuda_stream)
 
 
-def _shared_args(dims, packed, p, prec, deep_wgrad, window, p_drop, seeds, X, segments, adjacency, dev):
-    """What u2gnn_layer_fwd_csr and u2gnn_layer_bwd_csr take alike: (dims, params, seeds, X) in front, and the
-    attention pattern (segment offsets, their count, the CSR) that goes before the streams -- NULL, 0, NULL for a
-    layer with neither, which is the plain u2gnn_layer_fwd / u2gnn_layer_bwd call."""
+def _entry_bias(t, adjacency, dev, what):
+    """The pointer of a neighbour attention layer's per-entry bias (or its gradient): adjacency.nnz contiguous
+    float32 on the layer's device; None: NULL."""
+    if t is None:
+        return None
+    if (adjacency is None or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous()
+            or t.numel() != adjacency.nnz):
+        raise _lib.U2GNNNativeError(f"{what}: a contiguous float32 tensor of the adjacency's nnz entries on the "
+                                    "layer's device (and only with an adjacency)")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _shared_args(dims, packed, p, prec, deep_wgrad, window, p_drop, seeds, X, segments, adjacency, dev, bias=None):
+    """What u2gnn_layer_fwd_csrb and u2gnn_layer_bwd_csrb take alike: (dims, params, seeds, X) in front, and the
+    attention pattern (segment offsets, their count, the CSR, its per-entry bias) that goes before the streams --
+    NULL, 0, NULL, NULL for a layer with neither, which is the plain u2gnn_layer_fwd / u2gnn_layer_bwd call."""
     dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(p_drop, seeds)
     sp, ns = _segments(segments, dev)
     return ((ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr()),
-            (sp, ns, _adjacency(adjacency, dev) if adjacency is not None else None))
+            (sp, ns, _adjacency(adjacency, dev) if adjacency is not None else None,
+             _entry_bias(bias, adjacency, dev, "bias")))
 
 
 def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int, int], need_ctx: bool,
-                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None, adjacency=None):
+                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None, adjacency=None,
+                  bias=None):
     """window = 0: attention over all dims.N rows; W: within each node's window of W token rows
     (dims.N = nodes * W).  segments (int64 device [n_seg + 1] row offsets): every row attends over the rows
     of its own segment (per-graph attention); not together with window.  adjacency (core.Adjacency): every row
-    attends over the columns of its CSR row (neighbour attention); not together with window or segments."""
+    attends over the columns of its CSR row (neighbour attention); not together with window or segments.  bias (f32
+    device [adjacency.nnz], only with an adjacency): added to the entries' scores before the softmax."""
     pd = p_enc if train else 0.0
     nnz = adjacency.nnz if adjacency is not None else 0
     cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window, segments is not None, nnz)
@@ -161,21 +176,25 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
     X2 = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32)
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
-    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, window, pd, seeds, X, segments, adjacency, dev)
-    check(hip_lib().u2gnn_layer_fwd_csr(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                        ws.data_ptr(), ws.numel(), *pattern, _stream()), "u2gnn_layer_fwd_csr")
+    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, window, pd, seeds, X, segments, adjacency, dev,
+                                 bias)
+    check(hip_lib().u2gnn_layer_fwd_csrb(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                         ws.data_ptr(), ws.numel(), *pattern, _stream()), "u2gnn_layer_fwd_csrb")
     ctx = None
     if need_ctx:
         ctx = NativeCtx()
         ctx.X, ctx.buf, ctx.p_drop, ctx.seeds, ctx.window, ctx.segments = X, buf, pd, dict(seeds), window, segments
-        ctx.adjacency = adjacency
+        ctx.adjacency, ctx.bias = adjacency, bias
     return X2, ctx
 
 
 def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: str,
                    side: Optional["torch.cuda.Stream"] = None, deep_wgrad: bool = True,
-                   need_dx: bool = True, segments=None, adjacency=None) -> Optional[torch.Tensor]:
-    """segments / adjacency: None = the forward's (kept in ctx); given, it must be the forward's."""
+                   need_dx: bool = True, segments=None, adjacency=None, dbias=None) -> Optional[torch.Tensor]:
+    """segments / adjacency: None = the forward's (kept in ctx); given, it must be the forward's.  The forward's bias
+    is taken from ctx; dbias (f32 device [adjacency.nnz], only for a forward with a bias) receives its gradient."""
+    if dbias is not None and ctx.bias is None:
+        raise _lib.U2GNNNativeError("layer_backward: dbias given for a forward that ran without a bias")
     if adjacency is None:
         adjacency = ctx.adjacency
     elif ctx.adjacency is None:
@@ -190,12 +209,12 @@ def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: 
     dX = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32) if need_dx else None
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
     head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, ctx.window, ctx.p_drop, ctx.seeds, ctx.X, segments,
-                                 adjacency, dev)
+                                 adjacency, dev, ctx.bias)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
-    check(hip_lib().u2gnn_layer_bwd_csr(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
-                                        dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(), ws.numel(),
-                                        *pattern, _stream(), _stream(side) if side is not None else None),
-          "u2gnn_layer_bwd_csr")
+    check(hip_lib().u2gnn_layer_bwd_csrb(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
+                                         dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(),
+                                         ws.numel(), *pattern, _entry_bias(dbias, adjacency, dev, "dbias"), _stream(),
+                                         _stream(side) if side is not None else None), "u2gnn_layer_bwd_csrb")
     if side is not None:
         for t in (ws, ctx.buf, ctx.X, dX2):
             t.record_stream(side)

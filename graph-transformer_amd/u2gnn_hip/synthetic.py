@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .batching import HostBatch, csr_with_self
+from .batching import HostBatch, batch_hop_lists, check_hops_range, csr_with_self, hop_lists
 
 
 class SyntheticStore:
@@ -68,10 +68,21 @@ class SyntheticStore:
     def degrees_of(self, ids):
         return np.concatenate([self.graph(int(i))[2] for i in ids])
 
-    def adjacency(self, graph_ids):
+    def adjacency(self, graph_ids, hops=None):
         """GraphStore.adjacency for the synthetic graphs: (rowptr, colidx) of the batch, every row itself plus its
-        neighbours, sorted and without repeats; nothing is drawn from any RNG."""
+        neighbours, sorted and without repeats; nothing is drawn from any RNG.  hops = H: (rowptr, colidx, etype) of
+        the H-hop lists, as GraphStore.adjacency(ids, hops=H) (per-graph lists kept in the store)."""
         ids = np.asarray(graph_ids, dtype=np.int64)
+        if hops is not None:
+            hops = check_hops_range(hops)
+            cache = self.__dict__.setdefault("_hop_cache", {}).setdefault(hops, {})
+            lists = []
+            for g in ids:
+                if int(g) not in cache:
+                    start, nbr, deg, _ = self.graph(int(g))
+                    cache[int(g)] = hop_lists(len(deg), deg, start[:-1], nbr, hops)
+                lists.append(cache[int(g)])
+            return batch_hop_lists(lists, self.n_nodes[ids])
         parts = [self.graph(int(i)) for i in ids]
         offsets = np.zeros(len(ids) + 1, dtype=np.int64)
         np.cumsum(self.n_nodes[ids], out=offsets[1:])

@@ -29,7 +29,8 @@ class UnSupCore:
         self.T = module.num_self_att_layers
         self.p_out = module.dropout_p
         self.stack = EncoderStack(module.u2gnn_layers, self.d, self.ff, self.T, self.L, precision, 0.5,
-                                  getattr(module, "attention", "nodes"))
+                                  getattr(module, "attention", "nodes"), getattr(module, "hops", None),
+                                  lambda: module.hop_bias)
 
     def encode(self, b: DeviceBatch, train: bool, need_ctx: bool, seed: int, p: float = 0.0, drop_seed: int = 0):
         """-> (OV f32 [N, d*L] real layout, dropped out with (p, drop_seed) when p > 0, ctx).  The padded

@@ -592,6 +592,38 @@ int u2gnn_csr_attn_fwd(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_cs
 int u2gnn_csr_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_csr_attn *A, const float *O,
                        const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed, float q_scale,
                        float *dQKV, int64_t ldg, float *edge_ws, int64_t N, int64_t rows_pad, void *stream);
+/* The same two calls with a per-entry additive bias (ABI 19 grew by these entry points, nothing else changed):
+ * the score of entry e is Qs_i . K_col(e) + bias[e], bias: nnz DEVICE floats in colidx order (a column listed twice
+ * counts twice, each entry with its own bias).  The values must be finite; they are not scanned, and any content is
+ * memory-safe (bias is indexed by entry ids only).  The backward recomputes P with the same bias and, when dbias is
+ * not NULL, also writes dL/dbias[e] = dS_e into dbias (nnz floats).  bias == NULL (and dbias == NULL) is
+ * u2gnn_csr_attn_fwd / _bwd exactly (those forward here); dbias without bias: U2GNN_E_ARG. */
+int u2gnn_csr_attn_fwd_bias(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_csr_attn *A, const float *bias,
+                            float *O, int64_t ldo, float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad,
+                            void *stream);
+int u2gnn_csr_attn_bwd_bias(const float *QKV, int64_t ldq, int32_t dp, const u2gnn_csr_attn *A, const float *bias,
+                            const float *O, const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed,
+                            float q_scale, float *dQKV, int64_t ldg, float *edge_ws, float *dbias, int64_t N,
+                            int64_t rows_pad, void *stream);
+/* The bias as R small tables (one per encoder layer) over entry types (the hop distance of an entry, etype: DEVICE
+ * int32 [nnz]), n_types <= U2GNN_BIAS_TYPES_MAX.  Deterministic, no atomics.
+ * u2gnn_bias_expand: out[r][e] = tables[r][etype[e]] (tables [R][n_types], out [R][ld_out >= nnz]); a type outside
+ * [0, n_types) gives 0.  One launch.
+ * u2gnn_bias_table_grad: dtables[r][t] = sum over the entries e with etype[e] == t of dbias[r][e] (dbias [R][ld],
+ * ld >= nnz, ld % 4 == 0, dbias and etype 16-byte aligned: else U2GNN_E_ALIGN); entries with a type outside
+ * [0, n_types) are skipped, every dtables[r][t < n_types] is written (0 for a type without entries).  Two launches:
+ * every block sums 4096 consecutive entries per type in a fixed order into ws, then one block per table combines the
+ * blocks' partial sums in a fixed order.  No value passes through more than 128 sequential adds and 16 tree levels,
+ * which holds up to 4096 * 112 * 256 entries (more: U2GNN_E_SHAPE).  ws: u2gnn_bias_table_grad_ws_floats(R, n_types,
+ * nnz) floats (host-only; -1 for arguments the call below refuses).
+ * Null pointers, R < 1, n_types outside [1, U2GNN_BIAS_TYPES_MAX], nnz < 1, ld < nnz, a workspace that is too small:
+ * U2GNN_E_ARG before anything is launched. */
+#define U2GNN_BIAS_TYPES_MAX 32
+int u2gnn_bias_expand(const float *tables, int32_t R, int32_t n_types, const int32_t *etype, int64_t nnz, float *out,
+                      int64_t ld_out, void *stream);
+int64_t u2gnn_bias_table_grad_ws_floats(int32_t R, int32_t n_types, int64_t nnz);
+int u2gnn_bias_table_grad(const float *dbias, int64_t ld, int32_t R, int32_t n_types, const int32_t *etype, int64_t nnz,
+                          float *dtables, float *ws, int64_t ws_floats, void *stream);
 
 /* ---- a3: one encoder layer (TransformerEncoderLayer(d, nhead=1, ff, dropout), post-LN, slot-0
  * rows) issued natively: forward and backward of pytorch_U2GNN_Sup.py:19-21,35 /
@@ -685,6 +717,20 @@ int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
                         int32_t n_seg, const u2gnn_csr_attn *A, void *stream, void *side_stream);
+/* The _csr calls with the layer's per-entry attention bias (u2gnn_csr_attn_*_bias; ABI 19 grew by these entry points,
+ * nothing else changed): bias, A->nnz device floats, and in the backward dbias (A->nnz floats, caller-owned, may be
+ * NULL), which receives dL/dbias.  The sizes are u2gnn_layer_sizes_csr's: nothing of the bias lives in ctx or the
+ * workspaces.  bias == NULL and dbias == NULL is the _csr call exactly (the _csr calls forward here); bias without A,
+ * or dbias without bias: U2GNN_E_ARG before anything is launched. */
+int u2gnn_layer_fwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                         const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, const float *bias,
+                         void *stream);
+int u2gnn_layer_bwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                         int32_t n_seg, const u2gnn_csr_attn *A, const float *bias, float *dbias, void *stream,
+                         void *side_stream);
 
 /* ---- ABI v19: the executor's launch rules, for callers that issue the same kernels themselves (engine.py) ----
  * Host-only, like u2gnn_layer_sizes: no HIP call, usable without a GPU.  u2gnn_layer_plan: the shape rules of the

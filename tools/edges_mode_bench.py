@@ -9,7 +9,13 @@
     every entry reads one K and one V row forward (nnz * dp * 4 * 2 B) and K, V, Qs, dO rows backward (twice that),
     beside the dense QKV / O / dO / dQKV traffic and the entries' indices and (backward) Pd, dS values.
 
-Prints one JSON line.  Usage: python tools/edges_mode_bench.py [--steps 24] [--warmup 5] [--batches 4]"""
+--hops 1,2,3 adds, per H, the step of attention="edges" with hops=H (the H-hop pattern and the learned hop bias)
+beside the three modes in the same rotation, and per batch and H: nnz, the CSR forward / backward on that pattern
+without a bias and with a zero bias (the BIAS instantiations at equal arithmetic), and the u2gnn_bias_expand and
+u2gnn_bias_table_grad launches for the step's T tables.  --settings picks the settings to run.
+
+Prints one JSON line.  Usage: python tools/edges_mode_bench.py [--steps 24] [--warmup 5] [--batches 4] [--hops 1,2]
+[--settings c4,mutag]"""
 import argparse
 import json
 import math
@@ -50,7 +56,26 @@ def graph_time_us(fn):
     return e0.elapsed_time(e1) * 1e3 / REPS
 
 
-def kernel_figures(offsets, adj, d):
+def bias_figures(adj, d, T, QKV, dO, O, stats, dQKV, N, Np, dp):
+    """The kernels of the hop bias on one batch's H-hop pattern: the CSR forward / backward without and with a (zero)
+    bias, and the two table kernels for T tables."""
+    nnz, ld = adj.nnz, (adj.nnz + 3) // 4 * 4
+    bias, dbias = torch.zeros(nnz, device="cuda"), torch.empty(nnz, device="cuda")
+    qs = 1 / math.sqrt(d)
+    out = {"nnz": nnz, "n_types": adj.n_types,
+           "fwd_us": graph_time_us(lambda: K.csr_attn_fwd(QKV, dp, adj, O, stats, 0.5, 7, N, Np)),
+           "fwd_bias_us": graph_time_us(lambda: K.csr_attn_fwd_bias(QKV, dp, adj, bias, O, stats, 0.5, 7, N, Np)),
+           "bwd_us": graph_time_us(lambda: K.csr_attn_bwd(QKV, dp, adj, O, dO, stats, 0.5, 7, qs, dQKV, N, Np)),
+           "bwd_bias_us": graph_time_us(lambda: K.csr_attn_bwd_bias(QKV, dp, adj, bias, O, dO, stats, 0.5, 7, qs, dQKV,
+                                                                   dbias, N, Np))}
+    tables, dtables = torch.zeros(T, adj.n_types, device="cuda"), torch.empty(T, adj.n_types, device="cuda")
+    all_b = torch.empty(T, ld, device="cuda")
+    out["bias_expand_us"] = graph_time_us(lambda: K.bias_expand(tables, adj.etype, all_b))
+    out["bias_table_grad_us"] = graph_time_us(lambda: K.bias_table_grad(all_b, adj.etype, dtables))
+    return {k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}
+
+
+def kernel_figures(offsets, adj, d, hop_adjs=None, T=4):
     from u2gnn_hip.engine import row_pad, rup
     N, dp, nnz = int(offsets[-1]), rup(d, 64), adj.nnz
     Np = row_pad(N)
@@ -70,26 +95,34 @@ def kernel_figures(offsets, adj, d):
             "fwd_us": round(fwd, 2), "fwd_gather_mb": round(f_gather / 1e6, 2),
             "fwd_gather_gbs": round(f_gather / fwd / 1e3, 1), "fwd_gflops": round(f_flop / fwd / 1e3, 1),
             "bwd_us": round(bwd, 2), "bwd_gather_mb": round(b_gather / 1e6, 2),
-            "bwd_gather_gbs": round(b_gather / bwd / 1e3, 1), "bwd_gflops": round(b_flop / bwd / 1e3, 1)}
+            "bwd_gather_gbs": round(b_gather / bwd / 1e3, 1), "bwd_gflops": round(b_flop / bwd / 1e3, 1),
+            "hops": {str(h): bias_figures(a, d, T, QKV, dO, O, stats, dQKV, N, Np, dp)
+                     for h, a in (hop_adjs or {}).items()}}
 
 
-def time_steps(batches, d, C, T, ff, precision, args):
+def time_steps(batches, d, C, T, ff, precision, args, hop_batches=None):
+    """hop_batches: {H: the batches with the H-hop adjacency}; each adds the variant "edges_hH" (hops=H) to the
+    rotation."""
     from pytorch_U2GNN_Sup import TransformerU2GNN
     from u2gnn_hip.train import SupTrainer
-    trainers = {}
-    for mode in MODES:
+    variants = [(m, m, None, batches) for m in MODES]
+    variants += [(f"edges_h{h}", "edges", h, bs) for h, bs in (hop_batches or {}).items()]
+    names = tuple(v[0] for v in variants)
+    trainers, feed = {}, {}
+    for name, mode, hops, bs in variants:
         torch.manual_seed(123)
-        m = TransformerU2GNN(d, ff, C, T, 0.5, 1, precision=precision, attention=mode).cuda().train()
-        trainers[mode] = SupTrainer(m, lr=5e-4, max_norm=0.5, seed=123)
+        m = TransformerU2GNN(d, ff, C, T, 0.5, 1, precision=precision, attention=mode, hops=hops).cuda().train()
+        trainers[name], feed[name] = SupTrainer(m, lr=5e-4, max_norm=0.5, seed=123), bs
     nb = len(batches)
-    for tr in trainers.values():
+    for name, tr in trainers.items():
         for i in range(args.warmup):
-            tr.step(batches[i % nb])
+            tr.step(feed[name][i % nb])
     torch.cuda.synchronize()
-    times = {m: [] for m in MODES}
+    times = {m: [] for m in names}
     done, blk = 0, 0
     while done < args.steps:
-        order = MODES[blk % 3:] + MODES[:blk % 3]
+        r = blk % len(names)
+        order = names[r:] + names[:r]
         n = min(args.block, args.steps - done)
         for mode in order:
             tr = trainers[mode]
@@ -97,7 +130,7 @@ def time_steps(batches, d, C, T, ff, precision, args):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
                 e0.record()
-                tr.step(batches[(done + i) % nb])
+                tr.step(feed[mode][(done + i) % nb])
                 e1.record()
                 torch.cuda.synchronize()
                 times[mode].append(e0.elapsed_time(e1))
@@ -114,19 +147,27 @@ def setting(name, store, C, batch_size, k, args):
     np.random.seed(123)
     loader = BatchLoader(store, batch_size, k)
     host = [loader() for _ in range(args.batches)]
-    batches = []
+    batches, hop_batches = [], {H: [] for H in args.hops}
     for h in host:
         b = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
         b.adj = Adjacency.from_csr(*store.adjacency(h.graph_ids), b.N, device="cuda")
         batches.append(b)
+        for H in args.hops:
+            rowptr, colidx, etype = store.adjacency(h.graph_ids, hops=H)
+            hb = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
+            hb.adj = Adjacency.from_csr(rowptr, colidx, hb.N, device="cuda", etype=etype)
+            hop_batches[H].append(hb)
     d = host[0].X_concat.shape[1]
-    med, rng = time_steps(batches, d, C, T, ff, args.precision, args)
+    med, rng = time_steps(batches, d, C, T, ff, args.precision, args, hop_batches)
     out = {"setting": f"{name}: bs {batch_size}, k {k}, d {d}, T {T}, ff {ff}, {args.precision}, {len(host)} batches, "
                       f"eager steps, median of {args.steps} per mode in rotating blocks of {args.block}",
            "step_ms": med, "step_ms_min_max": rng,
            "edges_over_nodes": round(med["edges"] / med["nodes"], 4),
            "edges_over_graphs": round(med["edges"] / med["graphs"], 4),
-           "kernels": [kernel_figures(h.offsets, b.adj, d) for h, b in list(zip(host, batches))[:2]]}
+           "nnz": {"edges": [b.adj.nnz for b in batches],
+                   **{f"edges_h{H}": [b.adj.nnz for b in bs] for H, bs in hop_batches.items()}},
+           "kernels": [kernel_figures(h.offsets, b.adj, d, {H: bs[i].adj for H, bs in hop_batches.items()}, T)
+                       for i, (h, b) in enumerate(list(zip(host, batches))[:2])]}
     return out
 
 
@@ -137,14 +178,21 @@ def main():
     ap.add_argument("--batches", type=int, default=4)
     ap.add_argument("--block", type=int, default=4, help="steps per rotation block")
     ap.add_argument("--precision", default="fwdh")
+    ap.add_argument("--hops", default="", help="comma-separated H values: also time attention='edges' with hops=H")
+    ap.add_argument("--settings", default="c4,mutag", help="which of c4, mutag to run")
     args = ap.parse_args()
+    args.hops = [int(h) for h in args.hops.split(",") if h]
+    which = args.settings.split(",")
     assert torch.cuda.is_available(), "needs an MI355X: a timing without one would mean nothing"
     import util
     from u2gnn_hip.batching import GraphStore
     from u2gnn_hip.synthetic import collab_like
     graphs, C = util.load_data("MUTAG", False)
-    out = {"c4": setting("C4 synthetic", collab_like(seed=0), 3, 64, 16, args),
-           "mutag": setting("MUTAG", GraphStore(graphs), C, 64, 16, args)}
+    out = {}
+    if "c4" in which:
+        out["c4"] = setting("C4 synthetic", collab_like(seed=0), 3, 64, 16, args)
+    if "mutag" in which:
+        out["mutag"] = setting("MUTAG", GraphStore(graphs), C, 64, 16, args)
     print(json.dumps(out), flush=True)
 
 
