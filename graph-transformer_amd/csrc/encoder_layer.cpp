@@ -34,6 +34,18 @@ inline int64_t rup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // padded rows: multiples of 256 from 1024 rows on (the N^2 products always get 256x128 blocks), else of 128
 inline int64_t rows_pad(int64_t N) { return N >= 1024 ? rup(N, 256) : rup(N, 128); }
 
+// the kernels that run a layer's attention core: make_dims decides, carve_ctx / layer_fwd / layer_bwd switch on it
+enum class Attn {
+    window,       // within each node's window of W rows (window_attn.hip)
+    segments,     // per-graph: every row over the rows of its own segment (segment_attn.hip), exact fp32
+    csr,          // neighbour attention: every row over the columns of its CSR row (csr_attn.hip), exact fp32
+    // node attention, every row over all N rows:
+    small,        // d <= 32, on the vector ALUs (u2gnn_attn_small_*, small_layer.hip): every precision, no N x N
+                  // image -- the matrix-core products would be >= 50 % padding (dp = 64)
+    fused,        // S = Q K^T, then one softmax -> dropout -> P.V pass (u2gnn_attn_softmax_pv, attn_fused.hip)
+    three_pass,   // scores, softmax + dropout, P.V (fp32 parity path, dp > 384, few rows)
+};
+
 struct Dims {
     int64_t N, d, ff, Np, dp, ffp;
     int prec;
@@ -53,10 +65,8 @@ struct Dims {
     // both caller-owned, null: none
     const float *csr_bias = nullptr;
     float *csr_dbias = nullptr;
+    Attn attn;   // set by make_dims; meaningful once pattern_ok has passed the pattern
 };
-
-// attention over a row pattern (segments or a CSR): the generic route with a statistics-saving fp32 attention kernel
-bool sparse_attn(const Dims &D) { return D.n_seg || D.csr_nnz; }
 
 // The attention pattern of a call (n_seg row segments, a CSR of nnz entries, or neither: the node-axis or window
 // layer).  Segments: offsets and count, both or neither.  CSR: none, or a complete one with at least one entry.  Never
@@ -72,10 +82,21 @@ bool pattern_ok(const Dims &D, bool plan) {
     return !csr || (A && A->rowptr && A->colidx && A->t_rowptr && A->t_src && A->t_eid && D.csr_nnz >= 1);
 }
 
+// the fused attention forward (u2gnn_attn_softmax_pv): node-axis attention in the matrix-core precisions with
+// dp <= 384 and at least kFusedMinNp padded rows
+// (f16x3 -- the fwdh policy -- runs fused: V as fp16 x2 rows from the in-projection, 3.024 vs 3.052 ms three-pass,
+// profiles/r06/h3g_fused_ab.txt; bf16x6 -- the fwd6 policy -- keeps the three-pass form: its fused kernel, ran
+// the C4 step at 3.42 / 3.43 ms against 3.40 unfused, and its exp2-based probabilities moved one boundary ReLU unit
+// of the test seed's step across 0; DESIGN.md section 7).  Few rows (C2's IMDBBINARY batches, Np = 128: ONE
+// workgroup walks every key) run the three-pass form, whose GEMM tiles spread over more CUs: C2 fwdh 0.424 ms
+// three-pass (r6h) vs 0.460 fused (r6i)
+constexpr int64_t kFusedMinNp = 1024;
+
 // a: checked by dims_ok; the pattern: to be checked by pattern_ok
-Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg, const u2gnn_csr_attn *csr, int64_t nnz) {
+Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg, const u2gnn_csr_attn *csr, int64_t nnz,
+               const float *bias = nullptr, float *dbias = nullptr) {
     Dims D;
-    D.seg = seg, D.n_seg = n_seg, D.csr = csr, D.csr_nnz = nnz;
+    D.seg = seg, D.n_seg = n_seg, D.csr = csr, D.csr_nnz = nnz, D.csr_bias = bias, D.csr_dbias = dbias;
     D.N = a->N;
     D.d = a->d;
     D.ff = a->ff;
@@ -91,6 +112,13 @@ Dims make_dims(const u2gnn_layer_dims *a, const int64_t *seg, int32_t n_seg, con
     if (a->precision == U2GNN_PREC_BF16X3 && (a->flags & U2GNN_LAYER_FWD_H3)) D.prec_fwd = U2GNN_PREC_F16X3;
     D.deep_wgrad = (a->flags & U2GNN_LAYER_DEEP_WGRAD) != 0;
     D.window = a->window;
+    const bool fused = D.Np >= kFusedMinNp && D.prec_fwd != U2GNN_PREC_F32 && D.prec_fwd != U2GNN_PREC_BF16X6 &&
+                       D.dp <= 384;
+    if (D.window) D.attn = Attn::window;
+    else if (n_seg) D.attn = Attn::segments;
+    else if (nnz) D.attn = Attn::csr;
+    else if (D.d <= 32) D.attn = Attn::small;
+    else D.attn = fused ? Attn::fused : Attn::three_pass;
     return D;
 }
 
@@ -138,26 +166,27 @@ struct Ctx {   // tensors saved by the forward for the backward
     float *stats;
 };
 
-// node attention for d <= 32 on the vector ALUs (u2gnn_attn_small_*, small_layer.hip): every precision, no
-// N x N image -- the matrix-core products would be >= 50 % padding (dp = 64)
-bool small_attn(const Dims &D) { return !D.window && !sparse_attn(D) && D.d <= 32; }
+bool small_attn(const Dims &D) { return D.attn == Attn::small; }
+bool fused_attn(const Dims &D) { return D.attn == Attn::fused; }
+// node attention through the N x N image (fused or three-pass)
+bool image_attn(const Dims &D) { return D.attn == Attn::fused || D.attn == Attn::three_pass; }
 // the forward tail (a3.3 + a3.4) of a mid-width layer with few rows as one row-block kernel + the slab LayerNorm
 // (mid_layer.hip; C2: 2 launches instead of 5)
-bool mid_tail(const Dims &D) { return !D.window && !sparse_attn(D) && D.d > 32 && D.dp <= 256 && D.Np <= 512; }
+bool mid_tail(const Dims &D) { return image_attn(D) && D.dp <= 256 && D.Np <= 512; }
 
 Ctx carve_ctx(Arena &A, const Dims &D) {
     Ctx c;
     // the small-width path projects straight into its compact attention context: no [Np][3 dp] image
     c.QKV = small_attn(D) ? nullptr : A.take<float>(D.Np * 3 * D.dp);
     c.Pd = c.Psave = c.stats = nullptr;
-    if (D.window)
-        c.Psave = A.take<float>(D.N * D.window);
-    else if (sparse_attn(D))
-        c.stats = A.take<float>(2 * D.Np);
-    else if (small_attn(D))
-        c.stats = A.take<float>(u2gnn_attn_small_ctx_floats(D.Np, D.d));
-    else
-        c.Pd = A.take<float>(D.Np * D.Np);
+    switch (D.attn) {
+    case Attn::window: c.Psave = A.take<float>(D.N * D.window); break;
+    case Attn::segments:
+    case Attn::csr: c.stats = A.take<float>(2 * D.Np); break;
+    case Attn::small: c.stats = A.take<float>(u2gnn_attn_small_ctx_floats(D.Np, D.d)); break;
+    case Attn::fused:
+    case Attn::three_pass: c.Pd = A.take<float>(D.Np * D.Np); break;
+    }
     c.O = A.take<float>(D.Np * D.dp);
     c.Z1 = A.take<float>(D.Np * D.dp);
     c.X1 = A.take<float>(D.Np * D.dp);
@@ -530,21 +559,7 @@ int in_proj_tile(const Dims &D) {
 bool fused_ln(const Dims &D) { return D.dp == 64 && D.prec_fwd != U2GNN_PREC_F32; }
 // one-stream layers in the matrix-core precisions: LayerNorm1's backward forms the attention backward's delta =
 // rowsum(dO * O); the fp32 parity path keeps u2gnn_rowdot, whose error does not grow with |X|
-bool ln1_forms_delta(const Dims &D) { return !D.window && !sparse_attn(D) && D.prec != U2GNN_PREC_F32; }
-
-// the fused attention forward (u2gnn_attn_softmax_pv): node-axis attention in the matrix-core precisions with
-// dp <= 384 and at least kFusedMinNp padded rows
-// (f16x3 -- the fwdh policy -- runs fused: V as fp16 x2 rows from the in-projection, 3.024 vs 3.052 ms three-pass,
-// profiles/r06/h3g_fused_ab.txt; bf16x6 -- the fwd6 policy -- keeps the three-pass form: its fused kernel, ran
-// the C4 step at 3.42 / 3.43 ms against 3.40 unfused, and its exp2-based probabilities moved one boundary ReLU unit
-// of the test seed's step across 0; DESIGN.md section 7).  Few rows (C2's IMDBBINARY batches, Np = 128: ONE
-// workgroup walks every key) run the three-pass form, whose GEMM tiles spread over more CUs: C2 fwdh 0.424 ms
-// three-pass (r6h) vs 0.460 fused (r6i)
-constexpr int64_t kFusedMinNp = 1024;
-bool fused_attn(const Dims &D) {
-    return D.Np >= kFusedMinNp && !D.window && !sparse_attn(D) && !small_attn(D) && D.prec_fwd != U2GNN_PREC_F32 &&
-           D.prec_fwd != U2GNN_PREC_BF16X6 && D.dp <= 384;
-}
+bool ln1_forms_delta(const Dims &D) { return (small_attn(D) || image_attn(D)) && D.prec != U2GNN_PREC_F32; }
 
 // every shape rule of the node-axis (or window) layer in one place: what u2gnn_layer_plan hands out
 u2gnn_layer_rules layer_plan(const Dims &D, float p_drop) {
@@ -601,22 +616,23 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         U2GNN_TRY(g.run(st, plan));
     }
     const float *Q = c.QKV, *Kt = Q ? Q + dp : nullptr, *V = Q ? Q + 2 * dp : nullptr;   // (no image: small path)
-    if (D.window) {
-        // paper semantics: attention inside each node's window of W neighbour tokens
+    switch (D.attn) {
+    case Attn::window:
         if (!plan)
             U2GNN_TRY(u2gnn_window_attn_fwd(c.QKV, 3 * dp, D.window, (int32_t)dp, c.O, dp, c.Psave, pd, s->attn,
                                             N / D.window, Np, st));
-    } else if (D.n_seg) {
-        // per-graph attention: every row over the rows of its own segment (segment_attn.hip), exact fp32
+        break;
+    case Attn::segments:
         if (!plan)
             U2GNN_TRY(u2gnn_segment_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dp, c.stats, pd, s->attn,
                                              N, Np, st));
-    } else if (D.csr_nnz) {
-        // neighbour attention: every row over the columns of its CSR row (csr_attn.hip), exact fp32
+        break;
+    case Attn::csr:
         if (!plan)
             U2GNN_TRY(u2gnn_csr_attn_fwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.csr, D.csr_bias, c.O, dp, c.stats, pd,
                                               s->attn, N, Np, st));
-    } else if (small_attn(D)) {
+        break;
+    case Attn::small:
         // d <= 32: the whole layer on the vector ALUs (small_layer.hip): in-projection, softmax -> dropout -> P.V
         // flash-style (the row statistics and a compact Q, K, V saved) and a3.3 + a3.4 -- 2 or 3 launches
         if (!plan) {
@@ -626,7 +642,8 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
                                             st));
             probe_mark(U2GNN_ROLE_PV, true, st, plan);
         }
-    } else if (fused) {
+        break;
+    case Attn::fused: {
         // a3.2 as S = Q K^T with the softmax row partials from the GEMM epilogue, then one fused
         // softmax -> dropout -> P.V pass that overwrites S with the signed image (attn_fused.hip)
         const int64_t ld_rp = Np / 32, groups = Np / 64;   // 64-column groups of the 256 / 128 tiles
@@ -645,7 +662,9 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
                                             u2gnn_attn_softmax_pv_ws_floats(N, Np, dp), N, Np, pd, s->attn, prec, st));
             probe_mark(U2GNN_ROLE_PV, true, st, plan);
         }
-    } else {
+        break;
+    }
+    case Attn::three_pass: {
         // a3.2 scores, softmax + dropout, P.V (fp32 parity path, dp > 384)
         float *S = W.take<float>(Np * Np);
         {
@@ -658,10 +677,10 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
                                              nullptr, 0, st));
         U2GNN_TRY(gemm_split(W, D, G(c.Pd, V, c.O, Np, dp, Np, Np, 3 * dp, dp, prec).clamp(drop).h3_a(h3_prob_exp(pd))
                                        .role(U2GNN_ROLE_PV), To(st)));
+        break;
     }
-    if (small_attn(D)) {
-        // a3.3 + a3.4: run by u2gnn_layer_small_fwd above
-    } else if (mid_tail(D)) {
+    }
+    if (mid_tail(D)) {
         // a3.3 + a3.4 in two launches: out-projection .. FFN2 partials per row block and hidden chunk, then the
         // slab LayerNorm2 (mid_layer.hip)
         const int64_t wsf = u2gnn_layer_tail_mid_ws_floats(Np, dp, ffp);
@@ -670,7 +689,7 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
             const u2gnn_small_tail_args t = tail_args(D, w, s, c, X, X2);
             U2GNN_TRY(u2gnn_layer_tail_mid_fwd(&t, mws, wsf, st));
         }
-    } else {
+    } else if (!small_attn(D)) {   // (the small-width layer: a3.3 + a3.4 ran in u2gnn_layer_small_fwd above)
         // a3.3 out-projection + dropout1 + residual, LayerNorm1
         const bool fuse_ln = fused_ln(D);
         {
@@ -816,33 +835,35 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
     // attention core
     const float *Q = c.QKV, *Kt = Q ? Q + dp : nullptr, *V = Q ? Q + 2 * dp : nullptr;   // (no image: small path)
     const float q_scale = (float)(1.0 / std::sqrt((double)d));
-    float *dQKV;
+    float *dQKV = tail ? small_dqkv : W.take<float>(Np * 3 * dp);
     hipEvent_t dv_done = nullptr;   // side-stream position after the dV product (in_dx waits for it)
-    if (D.window) {
-        dQKV = W.take<float>(Np * 3 * dp);
+    switch (D.attn) {
+    case Attn::window:
         if (!plan)
             U2GNN_TRY(u2gnn_window_attn_bwd(c.QKV, 3 * dp, D.window, (int32_t)dp, dO, dp, c.Psave, pd, s->attn,
                                             q_scale, dQKV, 3 * dp, N / D.window, Np, st));
-    } else if (D.n_seg) {
-        // per-graph attention: delta, dQ over query tiles, then dK, dV over key tiles (P recomputed from the statistics)
-        dQKV = W.take<float>(Np * 3 * dp);
+        break;
+    case Attn::segments: {
+        // delta, dQ over query tiles, then dK, dV over key tiles (P recomputed from the statistics)
         float *seg_delta = W.take<float>(Np);
         if (!plan)
             U2GNN_TRY(u2gnn_segment_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dO, dp, c.stats, pd,
                                              s->attn, q_scale, dQKV, 3 * dp, seg_delta, N, Np, st));
-    } else if (D.csr_nnz) {
-        // neighbour attention: delta, the entries' Pd and dS and dQ per query row, then dK, dV per key row over the
-        // transpose (P recomputed from the statistics)
-        dQKV = W.take<float>(Np * 3 * dp);
+        break;
+    }
+    case Attn::csr: {
+        // delta, the entries' Pd and dS and dQ per query row, then dK, dV per key row over the transpose (P
+        // recomputed from the statistics)
         float *edge_ws = W.take<float>(2 * D.csr_nnz);
         if (!plan)
             U2GNN_TRY(u2gnn_csr_attn_bwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.csr, D.csr_bias, c.O, dO, dp, c.stats, pd,
                                               s->attn, q_scale, dQKV, 3 * dp, edge_ws, D.csr_dbias, N, Np, st));
-    } else if (small_attn(D)) {
-        // d <= 32: dQ, dK, dV (P recomputed from the row statistics) and dX += dQKV W_in, run with the tail above
-        dQKV = small_dqkv;
-    } else {
-        dQKV = W.take<float>(Np * 3 * dp);
+        break;
+    }
+    case Attn::small:   // dQ, dK, dV (P recomputed from the row statistics) and dX += dQKV W_in ran with the tail above
+        break;
+    case Attn::fused:
+    case Attn::three_pass: {
         const bool dv_side = so != st;   // grouped with dQ / dK on this stream instead: 3.136-3.141 vs 3.068-3.098 ms
         // dV needs only Pd and dO: on the side stream it overlaps the dS -> dQ -> dK chain
         U2GNN_TRY(sd.fork());
@@ -866,6 +887,8 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
                                        .role(U2GNN_ROLE_DK), To(st).hold(att).pair()));
         U2GNN_TRY(flush(att, W, st));
         U2GNN_TRY(sd.wait(dv_done));   // dV before dX += dQKV W_in
+        break;
+    }
     }
     // in-projection
     if (need_dx && !small_attn(D))
@@ -918,13 +941,10 @@ int u2gnn_layer_sizes_csr(const u2gnn_layer_dims *dims, float p_drop, int32_t n_
     if (!dims_ok(dims) || !ctx_bytes || !fwd_ws_bytes || !bwd_ws_bytes) return U2GNN_E_ARG;
     const Dims D = make_dims(dims, nullptr, n_seg, nullptr, nnz);
     if (!pattern_ok(D, true)) return U2GNN_E_ARG;
-    u2gnn_layer_seeds s;
-    std::memset(&s, 0, sizeof(s));
+    u2gnn_layer_seeds s{};
     s.p_drop = p_drop;
-    u2gnn_layer_params w;
-    std::memset(&w, 0, sizeof(w));
-    u2gnn_layer_grads g;
-    std::memset(&g, 0, sizeof(g));
+    const u2gnn_layer_params w{};
+    const u2gnn_layer_grads g{};
     Arena C(nullptr, 0), Wf(nullptr, 0), Wb(nullptr, 0), Cb(nullptr, 0);
     layer_fwd(D, &w, &s, nullptr, nullptr, C, Wf, true, nullptr);
     layer_bwd(D, &w, &s, nullptr, Cb, nullptr, nullptr, &g, Wb, nullptr, nullptr);
@@ -949,8 +969,7 @@ int u2gnn_layer_fwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params 
                          const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, const float *bias,
                          void *stream) {
     if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
-    D.csr_bias = bias;
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias);
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     return plan_then_run(ctx, ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
         return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
@@ -981,8 +1000,7 @@ int u2gnn_layer_bwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params 
                          int32_t n_seg, const u2gnn_csr_attn *A, const float *bias, float *dbias, void *stream,
                          void *side_stream) {
     if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0);
-    D.csr_bias = bias, D.csr_dbias = dbias;
+    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias, dbias);
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     // (planned with this call's schedule: its streams and whether dX is wanted)
     return plan_then_run(const_cast<void *>(ctx), ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {

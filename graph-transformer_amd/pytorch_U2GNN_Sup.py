@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, FlatParams, SupCore, check_hops, hop_bias_last
+from u2gnn_hip.core import DeviceBatch, FlatParams, SupCore, check_attention, check_hops, hop_bias_last
 
 
 class _SupFunction(torch.autograd.Function):
@@ -63,9 +63,7 @@ class TransformerU2GNN(nn.Module):
         self.num_U2GNN_layers = num_U2GNN_layers
         self.dropout_p = dropout
         self.precision = precision
-        if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
-        self.attention = attention
+        self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()

@@ -29,7 +29,7 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from sampled_softmax import SampledSoftmax
 from u2gnn_hip import kernels as K
-from u2gnn_hip.core import ATTENTION_MODES, DeviceBatch, check_hops, hop_bias_last
+from u2gnn_hip.core import DeviceBatch, check_attention, check_hops, hop_bias_last
 from u2gnn_hip.engine import site_seed
 from u2gnn_hip.unsup import SITE_SS_DROP, UnSupCore
 
@@ -77,9 +77,7 @@ class TransformerU2GNN(nn.Module):
             raise NotImplementedError("only sampler_type='default', loss_type='default' (graph-level U2GNN) "
                                       "are on the MI355X path; neighbour/contrastive/gae are node-level research")
         self.feature_dim_size = feature_dim_size
-        if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
-        self.attention = attention
+        self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size

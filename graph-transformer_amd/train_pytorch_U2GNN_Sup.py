@@ -126,11 +126,8 @@ def to_device(hb, store=train_store):
         b = DeviceBatch.from_store(hb, train_X, device=device)
     else:
         b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
-    if args.hops:                     # the H-hop lists and each entry's distance (hop_bias's index)
-        rowptr, colidx, etype = store.adjacency(hb.graph_ids, hops=args.hops)
-        b.adj = Adjacency.from_csr(rowptr, colidx, b.N, device=device, etype=etype)
-    elif args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
-        b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
+    if args.attention == "edges":   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists), from the store
+        b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
     return b
 
 

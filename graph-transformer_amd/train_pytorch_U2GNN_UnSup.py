@@ -140,11 +140,8 @@ def train():
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
         b = DeviceBatch.from_store(hb, store_X, device=device)
-        if args.hops:                     # the H-hop lists and each entry's distance (hop_bias's index)
-            rowptr, colidx, etype = store.adjacency(hb.graph_ids, hops=args.hops)
-            b.adj = Adjacency.from_csr(rowptr, colidx, b.N, device=device, etype=etype)
-        elif args.attention == "edges":   # the batch's adjacency (plus the diagonal), built on the host from the store
-            b.adj = Adjacency.from_csr(*store.adjacency(hb.graph_ids), b.N, device=device)
+        if args.attention == "edges":   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
+            b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]
         sid = torch.from_numpy(draws[run.rank]).to(device)

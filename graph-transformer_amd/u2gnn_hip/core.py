@@ -1,6 +1,8 @@
 """Model-level orchestration of the U2GNN hot path on the gfx950 kernels.
 
 * ``DeviceBatch``   — one mini-batch resident in HBM (input_x, X_concat, pooling CSR, labels).
+* ``EncoderStack``  — the L x T encoder layers under one attention pattern per batch (pattern.AttnPattern, chosen by
+                      ``_pattern`` from the model's ``attention``): one forward and one backward loop for every mode.
 * ``SupCore``       — forward / backward of pytorch_U2GNN_Sup.TransformerU2GNN (:30-46):
                       gather -> L x (T encoder layers -> sum-pool -> dropout -> Linear, summed).
 * ``FlatParams``    — all parameters (and grads, Adam moments) in single flat fp32 buffers,
@@ -18,10 +20,11 @@ import torch
 
 from . import kernels as K
 from . import native
-from ._lib import BIAS_TYPES_MAX
 from .engine import deep_wgrad as engine_deep_wgrad
 from .engine import (SITE_ATTN, SITE_DROP1, SITE_DROP2, SITE_DROPFF, SITE_HEAD, Dims, LayerParams, PackedLayer,
                      OffPath, encoder_layer_backward, encoder_layer_forward, rup, side_stream_pays, site_seed)
+# (Adjacency, check_hops, ATTENTION_MODES: re-exported, the models, tools and tests import them from here)
+from .pattern import ATTENTION_MODES, NODES, Adjacency, AttnPattern, check_attention, check_hops  # noqa: F401
 
 
 _IOTA = {}
@@ -45,62 +48,6 @@ def _pool_iota(N: int, dev: torch.device):
         n = max(N, 1 << 14, 2 * (c[0].numel() if c is not None else 0))
         c = _IOTA[key] = (torch.arange(n, device=dev, dtype=torch.int64), torch.ones(n, device=dev, dtype=torch.float32))
     return c[0][:N], c[1][:N]
-
-
-class Adjacency:
-    """The attention pattern of attention="edges" on the device: row i attends over colidx[rowptr[i] .. rowptr[i+1])
-    (GraphStore.adjacency: the node itself and its graph neighbours), with the transpose the backward walks: for
-    column j the entries e = t_eid[t] (indices into colidx) and their rows t_src[t], t in t_rowptr[j] ..
-    t_rowptr[j+1].  Five int64 tensors and nnz; the kernels never hand them back to the host.  With ``hops``
-    (GraphStore.adjacency(ids, hops=H)) also etype, int32 [nnz]: the shortest-path distance of each entry, the index
-    into the model's hop_bias tables, and n_types = max(etype) + 1."""
-    __slots__ = ("N", "nnz", "rowptr", "colidx", "t_rowptr", "t_src", "t_eid", "etype", "n_types", "_c")
-
-    def __init__(self, N, rowptr, colidx, t_rowptr, t_src, t_eid, etype=None, n_types=0):
-        self.N, self.nnz = int(N), int(colidx.numel())
-        self.rowptr, self.colidx, self.t_rowptr, self.t_src, self.t_eid = rowptr, colidx, t_rowptr, t_src, t_eid
-        self.etype, self.n_types = etype, int(n_types)
-        self._c = None
-
-    @staticmethod
-    def from_csr(rowptr, colidx, N: int, device="cuda", etype=None) -> "Adjacency":
-        """Validates the CSR on the host (ValueError: rowptr not [N+1], not starting at 0, decreasing or not ending
-        at len(colidx); a column outside [0, N); etype not one value per entry or outside [0, 32)), builds the
-        transpose by a stable argsort of the columns (the entries of a column keep their row order) and moves the
-        five arrays (and etype, as int32) to ``device``."""
-        rp = np.ascontiguousarray(np.asarray(rowptr), dtype=np.int64).reshape(-1)
-        ci = np.ascontiguousarray(np.asarray(colidx), dtype=np.int64).reshape(-1)
-        N = int(N)
-        if N < 1 or rp.shape[0] != N + 1:
-            raise ValueError(f"adjacency: rowptr must hold N + 1 = {N + 1} entries, got {rp.shape[0]}")
-        if rp[0] != 0 or rp[-1] != ci.shape[0] or (np.diff(rp) < 0).any():
-            raise ValueError("adjacency: rowptr must start at 0, never decrease and end at len(colidx)")
-        if ci.shape[0] and (ci.min() < 0 or ci.max() >= N):
-            raise ValueError(f"adjacency: a column index outside [0, {N})")
-        et, n_types = None, 0
-        if etype is not None:
-            et = np.ascontiguousarray(np.asarray(etype), dtype=np.int64).reshape(-1)
-            if et.shape[0] != ci.shape[0]:
-                raise ValueError(f"adjacency: etype must hold one value per entry ({ci.shape[0]}), got {et.shape[0]}")
-            if et.shape[0] and (et.min() < 0 or et.max() >= BIAS_TYPES_MAX):
-                raise ValueError(f"adjacency: an entry type outside [0, {BIAS_TYPES_MAX})")
-            n_types = int(et.max()) + 1 if et.shape[0] else 0
-        order = np.argsort(ci, kind="stable")                       # entry ids grouped by column, rows ascending
-        t_rowptr = np.zeros(N + 1, dtype=np.int64)
-        np.cumsum(np.bincount(ci, minlength=N), out=t_rowptr[1:])
-        rows = np.repeat(np.arange(N, dtype=np.int64), np.diff(rp))
-        dev = torch.device(device)
-        h2d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)  # noqa: E731
-        et_dev = None if et is None else torch.from_numpy(et.astype(np.int32)).to(dev)
-        return Adjacency(N, h2d(rp), h2d(ci), h2d(t_rowptr), h2d(rows[order]), h2d(order), et_dev, n_types)
-
-    def c_struct(self):
-        """The u2gnn_csr_attn of these arrays (kept alive with them)."""
-        if self._c is None:
-            from ._lib import CsrAttn
-            self._c = CsrAttn(*[t.data_ptr() or None for t in (self.rowptr, self.colidx, self.t_rowptr, self.t_src,
-                                                               self.t_eid)], self.nnz)
-        return self._c
 
 
 @dataclass
@@ -243,9 +190,6 @@ def _check_range_host(input_x, N: int):
         raise IndexError("index out of range in self (input_x entry outside [0, N))")
 
 
-ATTENTION_MODES = ("nodes", "neighbors", "graphs", "edges")
-
-
 def hop_bias_last(named, prefix: str = ""):
     """A model's named_parameters() with ``hop_bias`` moved to the end.  torch lists a module's own parameters before
     its children's, which would put hop_bias first; last, every other parameter keeps its place in the flat buffer
@@ -261,17 +205,6 @@ def hop_bias_last(named, prefix: str = ""):
         yield held
 
 
-def check_hops(hops, attention: str) -> Optional[int]:
-    """The ``hops`` keyword of the models: None (off) or an H in [1, 31], and only with attention="edges"."""
-    if hops is None:
-        return None
-    if attention != "edges":
-        raise ValueError(f"hops needs attention='edges', got attention={attention!r}")
-    if int(hops) != hops or not 1 <= int(hops) <= BIAS_TYPES_MAX - 1:
-        raise ValueError(f"hops must be an integer in [1, {BIAS_TYPES_MAX - 1}], got {hops!r}")
-    return int(hops)
-
-
 class EncoderStack:
     """L U2GNN layers x T post-LN encoder layers on slot-0 rows, with the re-gather between
     U2GNN layers (pytorch_U2GNN_Sup.py:33-39; pytorch_U2GNN_UnSup.py:55-64)."""
@@ -281,9 +214,7 @@ class EncoderStack:
         """hops = H with attention="edges": every layer adds hop_bias()[l][t][distance] to its attention scores;
         hop_bias: a callable that returns the model's [L, T, H + 1] parameter (read where it lies at each forward)."""
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
-        if attention not in ATTENTION_MODES:
-            raise ValueError(f"attention must be 'nodes', 'neighbors', 'graphs' or 'edges', got {attention!r}")
-        self.attention = attention
+        self.attention = check_attention(attention)
         self.hops, self.hop_bias = check_hops(hops, attention), hop_bias
         self.packed = None
         # Python orchestration only: the three-pass attention forward where the fused kernel would run
@@ -292,6 +223,13 @@ class EncoderStack:
         # optional callable(prefix, stream): called once a layer's parameter gradients are
         # enqueued (on `stream`), e.g. dp.OverlappedGradAllReduce.layer_done
         self.grad_ready = None
+
+    @classmethod
+    def for_module(cls, module, precision: str = "fp32") -> "EncoderStack":
+        """The stack of a model module; encoder dropout is hard-coded to 0.5 (pytorch_U2GNN_Sup.py:20)."""
+        return cls(module.u2gnn_layers, module.feature_dim_size, module.ff_hidden_size, module.num_self_att_layers,
+                   module.num_U2GNN_layers, precision, 0.5, getattr(module, "attention", "nodes"),
+                   getattr(module, "hops", None), lambda: module.hop_bias)
 
     def layer_params(self, l, t) -> LayerParams:
         return LayerParams.from_encoder_layer(self.layers[l].layers[t])
@@ -305,133 +243,87 @@ class EncoderStack:
                 jobs += self.packed[l][t].jobs(self.layer_params(l, t))
         K.pack_padded_multi(jobs)      # one launch per 32 tensors
 
-    def forward(self, b: "DeviceBatch", train: bool, need_ctx: bool, seed: int):
-        """Returns (outs, ctx): outs[l] = padded [Np, dp] slot-0 output of U2GNN layer l."""
-        if self.attention == "neighbors":
-            return self._forward_neighbors(b, train, need_ctx, seed)
-        # "graphs": the "nodes" path with every layer's attention cut into the batch's graphs (b.rowptr, on the device)
-        segments = None
-        if self.attention == "graphs":
-            if not native.enabled():
-                raise NotImplementedError("per-graph attention runs on the native layer executor (U2GNN_NATIVE_LAYER=1)")
+    def _pattern(self, b: "DeviceBatch"):
+        """-> (pattern, W, stride): what a row of this batch's layers attends over (the one AttnPattern every layer
+        call of a forward takes), and the layers' row layout: W rows per node (row n * W + s = slot s of node n;
+        slot 0 is the node's output) gathered from input_x with ``stride``.  Validates the batch for the mode."""
+        mode = self.attention
+        if mode != "nodes" and not native.enabled():
+            raise NotImplementedError(f"attention={mode!r} runs on the native layer executor (U2GNN_NATIVE_LAYER=1)")
+        if mode == "neighbors":
+            # paper semantics (SURVEY.md §8(f) rank 4; U2GNN_tf/model_U2GNN_Sup_multi.py:14-45): every node attends
+            # over its own k+1 gathered neighbour tokens; each layer runs on all N*W tokens (the executor's window mode)
+            if not b.input_x.is_contiguous():
+                raise ValueError("input_x must be contiguous [N, k+1]")
+            W = b.input_x.shape[1]
+            return AttnPattern.window(W), W, 1
+        if mode == "graphs":
+            # the "nodes" path with every layer's attention cut into the batch's graphs (b.rowptr, on the device)
             if not b.rows_contiguous:
                 raise ValueError("attention='graphs' needs every graph's nodes as consecutive rows: graph_pool row g "
                                  "must hold the columns rowptr[g] .. rowptr[g+1]-1 and colidx must be 0..N-1 in order "
                                  "(DeviceBatch.from_offsets / from_store build such batches)")
-            segments = b.rowptr[:b.B + 1].contiguous()
-        # "edges": the "nodes" path with every row attending over its row of the batch's adjacency (b.adj, on the device)
-        adjacency = None
-        if self.attention == "edges":
-            if not native.enabled():
-                raise NotImplementedError("neighbour attention over the adjacency runs on the native layer executor "
-                                          "(U2GNN_NATIVE_LAYER=1)")
+            return AttnPattern.segments(b.rowptr[:b.B + 1].contiguous()), 1, b.idx_stride
+        if mode == "edges":
+            # the "nodes" path with every row attending over its row of the batch's adjacency (b.adj, on the device)
             if b.adj is None:
                 raise ValueError("attention='edges' needs the batch's adjacency: set DeviceBatch.adj = "
                                  "Adjacency.from_csr(*store.adjacency(graph_ids), N, device) (reference-style tensor "
                                  "inputs carry no edges)")
             if b.adj.N != b.N:
                 raise ValueError(f"attention='edges': the adjacency is over {b.adj.N} rows, the batch has {b.N}")
-            adjacency = b.adj
+            if self.hops and b.adj.etype is None:
+                raise ValueError("hops needs the entries' distances: Adjacency.from_csr(rowptr, colidx, N, device, "
+                                 "etype=etype) with (rowptr, colidx, etype) = store.adjacency(graph_ids, hops=H)")
+            if self.hops and b.adj.n_types > self.hops + 1:
+                raise ValueError(f"hops={self.hops}: the adjacency holds distances up to {b.adj.n_types - 1}")
+            return AttnPattern.csr(b.adj), 1, b.idx_stride
+        return NODES, 1, b.idx_stride
+
+    def forward(self, b: "DeviceBatch", train: bool, need_ctx: bool, seed: int):
+        """Returns (outs, ctx): outs[l] = padded [Np, dp] slot-0 output of U2GNN layer l."""
+        pattern, W, stride = self._pattern(b)
         # hops: the per-entry bias of all L * T layers, expanded from the tables in one launch.  The tables are read
         # where the parameter lies (the flat buffer under a trainer), so a replayed HIP graph sees Adam's updates
         bias_all = None
         if self.hops:
-            if adjacency.etype is None:
-                raise ValueError("hops needs the entries' distances: Adjacency.from_csr(rowptr, colidx, N, device, "
-                                 "etype=etype) with (rowptr, colidx, etype) = store.adjacency(graph_ids, hops=H)")
-            if adjacency.n_types > self.hops + 1:
-                raise ValueError(f"hops={self.hops}: the adjacency holds distances up to {adjacency.n_types - 1}")
             tables = self.hop_bias().detach().view(self.L * self.T, self.hops + 1)
-            bias_all = torch.empty(self.L * self.T, rup(adjacency.nnz, 4), device=tables.device, dtype=torch.float32)
-            K.bias_expand(tables, adjacency.etype, bias_all)
+            bias_all = torch.empty(self.L * self.T, rup(pattern.nnz, 4), device=tables.device, dtype=torch.float32)
+            K.bias_expand(tables, b.adj.etype, bias_all)
         dev = b.X_concat.device
         d, dp = self.d, rup(self.d, 64)
-        dims = Dims(b.N, d, self.ff)
-        Np = dims.Np
+        dims = Dims(b.N, d, self.ff)                                  # the node rows: outs, the heads
+        ldims = dims if W == 1 else Dims(b.N * W, d, self.ff)         # the layers' rows
+        Np, R, Rp = dims.Np, ldims.N, ldims.Np
         self._pack(dev)
-        X = torch.empty(Np, dp, device=dev, dtype=torch.float32)
-        K.gather_rows(b.X_concat, b.input_x, b.idx_stride, X, b.N, Np, d, dp, b.err)
+        slot0 = torch.arange(b.N, device=dev, dtype=torch.int64) * W if W > 1 else None
+        X = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
+        K.gather_rows(b.X_concat, b.input_x, stride, X, R, Rp, d, dp, b.err)
         outs, lctxs = [], []
         for l in range(self.L):
             lctx = []
             for t in range(self.T):
                 seeds = {s: site_seed(seed, l, t, s) for s in (SITE_ATTN, SITE_DROP1, SITE_DROPFF, SITE_DROP2)}
                 if native.enabled():
-                    X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
+                    X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), ldims, train, seeds,
                                                 need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(),
-                                                segments=segments, adjacency=adjacency,
-                                                bias=None if bias_all is None else
-                                                bias_all[l * self.T + t, :adjacency.nnz])
+                                                pattern=pattern, bias=None if bias_all is None else
+                                                bias_all[l * self.T + t, :pattern.nnz])
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                  need_ctx, self.prec, self.p_enc, three_pass=self.three_pass)
                 lctx.append(c)
+            if slot0 is not None:   # slot 0 of every node's window is the node's output
+                out = torch.empty(Np, dp, device=dev, dtype=torch.float32)
+                K.gather_rows(X, slot0, 1, out, b.N, Np, d, dp)
+                X = out
             outs.append(X)
             lctxs.append(lctx)
             if l + 1 < self.L:
-                Xn = torch.empty(Np, dp, device=dev, dtype=torch.float32)
-                K.gather_rows(X, b.input_x, b.idx_stride, Xn, b.N, Np, d, dp, b.err)
+                Xn = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
+                K.gather_rows(X, b.input_x, stride, Xn, R, Rp, d, dp, b.err)
                 X = Xn
-        return outs, {"dims": dims, "layers": lctxs, "batch": b}
-
-    # ---- paper semantics (SURVEY.md §8(f) rank 4; U2GNN_tf/model_U2GNN_Sup_multi.py:14-45): every
-    # node attends over its own k+1 gathered neighbour tokens.  Token rows are node-major
-    # (row n*W + s = slot s of node n, W = k+1); each layer runs on all N*W tokens through the native
-    # executor's window mode; slot 0 of the last layer is the node's output.
-    def _forward_neighbors(self, b: "DeviceBatch", train: bool, need_ctx: bool, seed: int):
-        if not native.enabled():
-            raise NotImplementedError("neighbour attention runs on the native layer executor (U2GNN_NATIVE_LAYER=1)")
-        dev = b.X_concat.device
-        d, dp = self.d, rup(self.d, 64)
-        if not b.input_x.is_contiguous():
-            raise ValueError("input_x must be contiguous [N, k+1]")
-        W = b.input_x.shape[1]
-        dims, tdims = Dims(b.N, d, self.ff), Dims(b.N * W, d, self.ff)
-        Np, R, Rp = dims.Np, b.N * W, tdims.Np
-        self._pack(dev)
-        slot0 = torch.arange(b.N, device=dev, dtype=torch.int64) * W
-        X = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
-        K.gather_rows(b.X_concat, b.input_x, 1, X, R, Rp, d, dp, b.err)
-        outs, lctxs = [], []
-        for l in range(self.L):
-            lctx = []
-            for t in range(self.T):
-                seeds = {s: site_seed(seed, l, t, s) for s in (SITE_ATTN, SITE_DROP1, SITE_DROPFF, SITE_DROP2)}
-                X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), tdims, train, seeds,
-                                            need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(), window=W)
-                lctx.append(c)
-            out = torch.empty(Np, dp, device=dev, dtype=torch.float32)
-            K.gather_rows(X, slot0, 1, out, b.N, Np, d, dp)
-            outs.append(out)
-            lctxs.append(lctx)
-            if l + 1 < self.L:
-                X = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
-                K.gather_rows(out, b.input_x, 1, X, R, Rp, d, dp, b.err)
-        return outs, {"dims": dims, "tdims": tdims, "window": W, "slot0": slot0, "layers": lctxs, "batch": b}
-
-    def _backward_neighbors(self, ctx, ext_grad, grads: dict, prefix: str):
-        b = ctx["batch"]
-        tdims, W, slot0 = ctx["tdims"], ctx["window"], ctx["slot0"]
-        d, dp = self.d, rup(self.d, 64)
-        R = b.N * W
-        off = OffPath(b.input_x.device, enabled=side_stream_pays(tdims))
-        dnext = None
-        for l in reversed(range(self.L)):
-            dOut = ext_grad(l)                                   # [Np, dp] node rows
-            if dnext is not None:                                # re-gather of the next U2GNN layer
-                K.scatter_add_rows(dnext, b.input_x, 1, dOut, R, d, b.err)
-            dX = torch.zeros(tdims.Np, dp, device=dOut.device, dtype=torch.float32)
-            K.scatter_add_rows(dOut, slot0, 1, dX, b.N, d)       # slot 0 of every node
-            for t in reversed(range(self.T)):
-                pre = f"{prefix}.{l}.layers.{t}."
-                g = LayerParams(*[grads[pre + k] for k in LAYER_KEYS])
-                dX = native.layer_backward(dX, ctx["layers"][l][t], self.packed[l][t], self.layer_params(l, t), g,
-                                           tdims, self.prec, side=off.side, deep_wgrad=engine_deep_wgrad(),
-                                           need_dx=l > 0 or t > 0)
-                self._layer_grads_done(pre, off, need_dx=l > 0 or t > 0)
-            dnext = dX
-        off.join()
-        return dnext
+        return outs, {"dims": dims, "layers": lctxs, "batch": b, "ldims": ldims, "stride": stride, "slot0": slot0}
 
     def _layer_grads_done(self, pre: str, off: OffPath, need_dx: bool) -> None:
         """Hand a layer's finished parameter-gradient region to ``grad_ready`` with a stream ordered after
@@ -452,20 +344,21 @@ class EncoderStack:
         """ext_grad(l) -> fresh padded gradient of outs[l] from outside the stack (head / loss).
         Writes encoder parameter gradients into grads[<reference key>]; returns None (the stack
         input, rows of X_concat, takes no gradient)."""
-        if "window" in ctx:
-            return self._backward_neighbors(ctx, ext_grad, grads, prefix)
         b = ctx["batch"]
-        dims = ctx["dims"]
+        ldims, stride, slot0 = ctx["ldims"], ctx["stride"], ctx["slot0"]
         dnext = None
-        off = OffPath(b.input_x.device, enabled=side_stream_pays(dims))
+        off = OffPath(b.input_x.device, enabled=side_stream_pays(ldims))
         # hops: every layer leaves dL/dbias of its entries in its row; one reduction to the tables after the last layer
         dbias_all = None
         if self.hops:
             dbias_all = torch.empty(self.L * self.T, rup(b.adj.nnz, 4), device=b.input_x.device, dtype=torch.float32)
         for l in reversed(range(self.L)):
-            dX = ext_grad(l)
-            if dnext is not None:
-                K.scatter_add_rows(dnext, b.input_x, b.idx_stride, dX, b.N, self.d, b.err)
+            dX = ext_grad(l)                                     # [Np, dp] node rows
+            if dnext is not None:                                # re-gather of the next U2GNN layer
+                K.scatter_add_rows(dnext, b.input_x, stride, dX, ldims.N, self.d, b.err)
+            if slot0 is not None:                                # the node's gradient enters at slot 0 of its window
+                dOut, dX = dX, torch.zeros(ldims.Np, ldims.dp, device=dX.device, dtype=torch.float32)
+                K.scatter_add_rows(dOut, slot0, 1, dX, b.N, self.d)
             for t in reversed(range(self.T)):
                 pre = f"{prefix}.{l}.layers.{t}."
                 g = LayerParams(*[grads[pre + k] for k in LAYER_KEYS])
@@ -473,13 +366,13 @@ class EncoderStack:
                 # the stack's input (gathered X_concat rows) is not trainable: no dX out of layer (0, 0)
                 need_dx = l > 0 or t > 0
                 if isinstance(lc, native.NativeCtx):
-                    dX = native.layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, dims,
+                    dX = native.layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, ldims,
                                                self.prec, side=off.side, deep_wgrad=engine_deep_wgrad(),
                                                need_dx=need_dx,
                                                dbias=None if dbias_all is None else
                                                dbias_all[l * self.T + t, :b.adj.nnz])
                 else:
-                    dX = encoder_layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, dims,
+                    dX = encoder_layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, ldims,
                                                 self.prec, off=off, need_dx=need_dx)
                 self._layer_grads_done(pre, off, need_dx)
             dnext = dX
@@ -494,17 +387,11 @@ class SupCore:
 
     def __init__(self, module, precision: str = "fp32"):
         self.m = module
-        self.prec = precision
         self.d = module.feature_dim_size
-        self.ff = module.ff_hidden_size
         self.C = module.num_classes
         self.L = module.num_U2GNN_layers
-        self.T = module.num_self_att_layers
         self.p_head = module.dropout_p        # args.dropout, pytorch_U2GNN_Sup.py:28
-        # encoder dropout is hard-coded to 0.5 (pytorch_U2GNN_Sup.py:20)
-        self.stack = EncoderStack(module.u2gnn_layers, self.d, self.ff, self.T, self.L, precision, 0.5,
-                                  getattr(module, "attention", "nodes"), getattr(module, "hops", None),
-                                  lambda: module.hop_bias)
+        self.stack = EncoderStack.for_module(module, precision)
 
     def forward(self, b: DeviceBatch, train: bool, need_ctx: bool, seed: int):
         dev = b.X_concat.device

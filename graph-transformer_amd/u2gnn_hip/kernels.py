@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check, hip_lib
+from .pattern import AttnPattern
 
 PREC = {"fp32": _lib.PREC_F32, "bf16x3": _lib.PREC_BF16X3, "bf16": _lib.PREC_BF16, "bf16x6": _lib.PREC_BF16X6,
         "f16x3": _lib.PREC_F16X3}
@@ -300,10 +301,8 @@ def segment_attn_bwd(QKV, dp, seg_offsets, O, dO, stats, p, seed, q_scale, dQKV,
 
 
 def _csr(adjacency, *tensors):
-    """The u2gnn_csr_attn of a core.Adjacency whose arrays live on the tensors' device."""
-    if adjacency is None or not adjacency.rowptr.is_cuda or adjacency.rowptr.device != tensors[0].device:
-        raise _lib.U2GNNNativeError("adjacency: a core.Adjacency on the tensors' device")
-    return ctypes.byref(adjacency.c_struct())
+    """The u2gnn_csr_attn of a pattern.Adjacency whose arrays live on the tensors' device (checked by its pattern)."""
+    return AttnPattern.csr(adjacency).c_args(tensors[0].device)[2]
 
 
 def csr_attn_fwd(QKV, dp, adjacency, O, stats, p, seed, N, rows_pad):

@@ -5,6 +5,7 @@ engine.py issues the same kernel sequence launch by launch from Python (kept as 
 reference orchestration and for per-GEMM event timing); this module is the production path.  Every tile, split
 count and threshold of that sequence is decided in the executor alone: engine.py asks layer_plan / split_plan
 below (u2gnn_layer_plan, u2gnn_gemm_split_plan; host-only calls, cached by their arguments).
+The rows a layer's rows attend over are one argument, a pattern.AttnPattern (NODES, window, segments or csr).
 Buffers come from the torch caching allocator: the forward's saved tensors live in one uint8
 "ctx" tensor per layer, workspaces are allocated per call.  Memory read by the backward's
 side stream is record_stream'ed so the allocator cannot recycle it early.
@@ -13,6 +14,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
@@ -20,6 +22,7 @@ import torch
 from . import _lib
 from ._lib import LayerDims, LayerGrads, LayerParamsC, LayerSeeds, check, hip_lib
 from .kernels import PREC
+from .pattern import NODES, AttnPattern
 
 _SIZES: Dict[tuple, tuple] = {}
 _LAYER_PLANS: Dict[tuple, _lib.LayerPlan] = {}
@@ -57,17 +60,16 @@ def _dims(N: int, d: int, ff: int, prec: str, deep_wgrad: bool, window: int = 0)
     return LayerDims(int(N), int(d), int(ff), PREC[prec], flags, int(window), 0)
 
 
-def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = True, window: int = 0,
-          segments: bool = False, nnz: int = 0):
-    """segments: the per-graph attention layer (the sizes depend on the mode only, never on the offsets); nnz > 0:
-    the neighbour attention layer over a CSR of nnz entries (its backward workspace holds 2 nnz floats)."""
-    key = (N, d, ff, prec, p_drop > 0, deep_wgrad, window, bool(segments), int(nnz))
+def sizes(N: int, d: int, ff: int, prec: str, p_drop: float, deep_wgrad: bool = True, pattern: AttnPattern = NODES):
+    """(ctx, forward workspace, backward workspace) bytes of a layer under ``pattern``: they depend on its kind, window
+    and nnz only (pattern.key), never on the offsets or the columns (the CSR backward workspace holds 2 nnz floats)."""
+    key = (N, d, ff, prec, p_drop > 0, deep_wgrad) + pattern.key
     r = _SIZES.get(key)
     if r is None:
         c, f, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        dims = _dims(N, d, ff, prec, deep_wgrad, window)
-        check(hip_lib().u2gnn_layer_sizes_csr(ctypes.byref(dims), float(p_drop), 1 if segments else 0, int(nnz),
-                                              ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
+        dims = _dims(N, d, ff, prec, deep_wgrad, pattern.W)
+        check(hip_lib().u2gnn_layer_sizes_csr(ctypes.byref(dims), float(p_drop), 1 if pattern.kind == "segments" else 0,
+                                              pattern.nnz, ctypes.byref(c), ctypes.byref(f), ctypes.byref(b)),
               "u2gnn_layer_sizes_csr")
         r = _SIZES[key] = (c.value, f.value, b.value)
     return r
@@ -112,108 +114,71 @@ def _seeds(p_drop: float, seeds: Dict[int, int]) -> LayerSeeds:
                       seeds.get(SITE_DROP2, 0))
 
 
-class NativeCtx:
-    """What the backward needs from one layer's forward."""
-    __slots__ = ("X", "buf", "p_drop", "seeds", "window", "segments", "adjacency", "bias")
-
-
-def _adjacency(adjacency, dev):
-    """The u2gnn_csr_attn of a neighbour attention layer's core.Adjacency (arrays on the layer's device)."""
-    if adjacency.nnz < 1 or not adjacency.rowptr.is_cuda or adjacency.rowptr.device != dev:
-        raise _lib.U2GNNNativeError("adjacency: a core.Adjacency with at least one entry on the layer's device")
-    return ctypes.byref(adjacency.c_struct())
-
-
-def _segments(segments, dev):
-    """(pointer, count) of a per-graph attention layer's row offsets: int64 device [n_seg + 1]."""
-    if segments is None:
-        return None, 0
-    if (not segments.is_cuda or segments.device != dev or segments.dtype != torch.int64 or segments.dim() != 1
-            or segments.numel() < 2 or not segments.is_contiguous()):
-        raise _lib.U2GNNNativeError("segments: a contiguous int64 tensor [n_seg + 1] on the layer's device")
-    return ctypes.c_void_p(segments.data_ptr()), segments.numel() - 1
+# what the backward needs from one layer's forward
+NativeCtx = namedtuple("NativeCtx", "X buf p_drop seeds pattern bias")
 
 
 def _stream(s=None):
     return ctypes.c_void_p((s or torch.cuda.current_stream()).cuda_stream)
 
 
-def _entry_bias(t, adjacency, dev, what):
-    """The pointer of a neighbour attention layer's per-entry bias (or its gradient): adjacency.nnz contiguous
+def _entry_bias(t, pattern, dev, what):
+    """The pointer of a neighbour attention layer's per-entry bias (or its gradient): pattern.nnz contiguous
     float32 on the layer's device; None: NULL."""
     if t is None:
         return None
-    if (adjacency is None or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous()
-            or t.numel() != adjacency.nnz):
+    if (pattern.kind != "csr" or not t.is_cuda or t.device != dev or t.dtype != torch.float32
+            or not t.is_contiguous() or t.numel() != pattern.nnz):
         raise _lib.U2GNNNativeError(f"{what}: a contiguous float32 tensor of the adjacency's nnz entries on the "
                                     "layer's device (and only with an adjacency)")
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _shared_args(dims, packed, p, prec, deep_wgrad, window, p_drop, seeds, X, segments, adjacency, dev, bias=None):
-    """What u2gnn_layer_fwd_csrb and u2gnn_layer_bwd_csrb take alike: (dims, params, seeds, X) in front, and the
-    attention pattern (segment offsets, their count, the CSR, its per-entry bias) that goes before the streams --
-    NULL, 0, NULL, NULL for a layer with neither, which is the plain u2gnn_layer_fwd / u2gnn_layer_bwd call."""
-    dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, window), _params(packed, p), _seeds(p_drop, seeds)
-    sp, ns = _segments(segments, dev)
-    return ((ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr()),
-            (sp, ns, _adjacency(adjacency, dev) if adjacency is not None else None,
-             _entry_bias(bias, adjacency, dev, "bias")))
+def _shared_args(dims, packed, p, prec, deep_wgrad, pattern, p_drop, seeds, X):
+    """(dims, params, seeds, X): what u2gnn_layer_fwd_csrb and u2gnn_layer_bwd_csrb take alike in front.  The attention
+    pattern that goes before the streams is pattern.c_args -- NULL, 0, NULL for a layer with neither segments nor a
+    CSR, which with a NULL bias is the plain u2gnn_layer_fwd / u2gnn_layer_bwd call."""
+    dd, pp, ss = _dims(dims.N, dims.d, dims.ff, prec, deep_wgrad, pattern.W), _params(packed, p), _seeds(p_drop, seeds)
+    return ctypes.byref(dd), ctypes.byref(pp), ctypes.byref(ss), X.data_ptr()
 
 
 def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int, int], need_ctx: bool,
-                  prec: str, p_enc: float, deep_wgrad: bool = True, window: int = 0, segments=None, adjacency=None,
-                  bias=None):
-    """window = 0: attention over all dims.N rows; W: within each node's window of W token rows
-    (dims.N = nodes * W).  segments (int64 device [n_seg + 1] row offsets): every row attends over the rows
-    of its own segment (per-graph attention); not together with window.  adjacency (core.Adjacency): every row
-    attends over the columns of its CSR row (neighbour attention); not together with window or segments.  bias (f32
-    device [adjacency.nnz], only with an adjacency): added to the entries' scores before the softmax."""
+                  prec: str, p_enc: float, deep_wgrad: bool = True, pattern: AttnPattern = NODES, bias=None):
+    """pattern (pattern.AttnPattern): the rows every row of X attends over -- NODES: all dims.N rows; window(W): its
+    node's W token rows (dims.N = nodes * W); segments(offsets): the rows of its own segment (per-graph attention);
+    csr(adjacency): the columns of its CSR row (neighbour attention).  bias (f32 device [pattern.nnz], only with a
+    csr pattern): added to the entries' scores before the softmax."""
     pd = p_enc if train else 0.0
-    nnz = adjacency.nnz if adjacency is not None else 0
-    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, window, segments is not None, nnz)
+    cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, pattern)
     dev = X.device
     X2 = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32)
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
-    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, window, pd, seeds, X, segments, adjacency, dev,
-                                 bias)
+    head = _shared_args(dims, packed, p, prec, deep_wgrad, pattern, pd, seeds, X)
     check(hip_lib().u2gnn_layer_fwd_csrb(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
-                                         ws.data_ptr(), ws.numel(), *pattern, _stream()), "u2gnn_layer_fwd_csrb")
-    ctx = None
-    if need_ctx:
-        ctx = NativeCtx()
-        ctx.X, ctx.buf, ctx.p_drop, ctx.seeds, ctx.window, ctx.segments = X, buf, pd, dict(seeds), window, segments
-        ctx.adjacency, ctx.bias = adjacency, bias
-    return X2, ctx
+                                         ws.data_ptr(), ws.numel(), *pattern.c_args(dev),
+                                         _entry_bias(bias, pattern, dev, "bias"), _stream()), "u2gnn_layer_fwd_csrb")
+    return X2, NativeCtx(X, buf, pd, dict(seeds), pattern, bias) if need_ctx else None
 
 
 def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: str,
                    side: Optional["torch.cuda.Stream"] = None, deep_wgrad: bool = True,
-                   need_dx: bool = True, segments=None, adjacency=None, dbias=None) -> Optional[torch.Tensor]:
-    """segments / adjacency: None = the forward's (kept in ctx); given, it must be the forward's.  The forward's bias
-    is taken from ctx; dbias (f32 device [adjacency.nnz], only for a forward with a bias) receives its gradient."""
+                   need_dx: bool = True, dbias=None) -> Optional[torch.Tensor]:
+    """The forward's pattern and bias are taken from ctx; dbias (f32 device [pattern.nnz], only for a forward with a
+    bias) receives the bias's gradient."""
     if dbias is not None and ctx.bias is None:
         raise _lib.U2GNNNativeError("layer_backward: dbias given for a forward that ran without a bias")
-    if adjacency is None:
-        adjacency = ctx.adjacency
-    elif ctx.adjacency is None:
-        raise _lib.U2GNNNativeError("layer_backward: an adjacency given for a forward that ran without one")
-    if segments is None:
-        segments = ctx.segments
-    elif ctx.segments is None:
-        raise _lib.U2GNNNativeError("layer_backward: segments given for a forward that ran without them")
-    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, ctx.window, segments is not None,
-                      adjacency.nnz if adjacency is not None else 0)
+    pattern = ctx.pattern
+    cb, _, bb = sizes(dims.N, dims.d, dims.ff, prec, ctx.p_drop, deep_wgrad, pattern)
     dev = dX2.device
     dX = torch.empty(dims.Np, dims.dp, device=dev, dtype=torch.float32) if need_dx else None
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
-    head, pattern = _shared_args(dims, packed, p, prec, deep_wgrad, ctx.window, ctx.p_drop, ctx.seeds, ctx.X, segments,
-                                 adjacency, dev, ctx.bias)
+    head = _shared_args(dims, packed, p, prec, deep_wgrad, pattern, ctx.p_drop, ctx.seeds, ctx.X)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
     check(hip_lib().u2gnn_layer_bwd_csrb(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
                                          dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(),
-                                         ws.numel(), *pattern, _entry_bias(dbias, adjacency, dev, "dbias"), _stream(),
+                                         ws.numel(), *pattern.c_args(dev), _entry_bias(ctx.bias, pattern, dev, "bias"),
+                                         _entry_bias(dbias, pattern, dev, "dbias"), _stream(),
                                          _stream(side) if side is not None else None), "u2gnn_layer_bwd_csrb")
     if side is not None:
         for t in (ws, ctx.buf, ctx.X, dX2):

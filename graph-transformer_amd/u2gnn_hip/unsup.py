@@ -24,13 +24,9 @@ class UnSupCore:
     def __init__(self, module, precision: str = "fp32"):
         self.m = module
         self.d = module.feature_dim_size
-        self.ff = module.ff_hidden_size
         self.L = module.num_U2GNN_layers
-        self.T = module.num_self_att_layers
         self.p_out = module.dropout_p
-        self.stack = EncoderStack(module.u2gnn_layers, self.d, self.ff, self.T, self.L, precision, 0.5,
-                                  getattr(module, "attention", "nodes"), getattr(module, "hops", None),
-                                  lambda: module.hop_bias)
+        self.stack = EncoderStack.for_module(module, precision)
 
     def encode(self, b: DeviceBatch, train: bool, need_ctx: bool, seed: int, p: float = 0.0, drop_seed: int = 0):
         """-> (OV f32 [N, d*L] real layout, dropped out with (p, drop_seed) when p > 0, ctx).  The padded

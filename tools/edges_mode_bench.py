@@ -150,12 +150,11 @@ def setting(name, store, C, batch_size, k, args):
     batches, hop_batches = [], {H: [] for H in args.hops}
     for h in host:
         b = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
-        b.adj = Adjacency.from_csr(*store.adjacency(h.graph_ids), b.N, device="cuda")
+        b.adj = Adjacency.from_store(store, h.graph_ids, b.N, "cuda")
         batches.append(b)
         for H in args.hops:
-            rowptr, colidx, etype = store.adjacency(h.graph_ids, hops=H)
             hb = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
-            hb.adj = Adjacency.from_csr(rowptr, colidx, hb.N, device="cuda", etype=etype)
+            hb.adj = Adjacency.from_store(store, h.graph_ids, hb.N, "cuda", hops=H)
             hop_batches[H].append(hb)
     d = host[0].X_concat.shape[1]
     med, rng = time_steps(batches, d, C, T, ff, args.precision, args, hop_batches)
