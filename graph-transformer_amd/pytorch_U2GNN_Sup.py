@@ -20,7 +20,9 @@ attends over its own k+1 sampled neighbours, U2GNN_tf/model_U2GNN_Sup_multi.py:1
 so a graph's scores do not depend on the other graphs of the batch; it needs each graph's nodes as
 consecutive rows, which ``forward`` checks on its graph_pool) or "edges" (a node attends over itself and its
 graph neighbours: the batch's adjacency plus the diagonal, ``DeviceBatch.adj`` =
-``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``; structure-aware without sampling and, as "graphs",
+``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``, or -- the same integers without the per-batch host
+work -- ``DeviceGraphs.from_store(store, device, hops)`` once per dataset and then ``graphs.adjacency(graph_ids)`` or
+``DeviceBatch.from_store(hb, X_dev, graphs=graphs)`` per batch; structure-aware without sampling and, as "graphs",
 independent of the batch; reference-style tensor inputs carry no edges, so ``forward`` raises a ValueError for them);
 ``hops`` = None, or H in [1, 31] with attention="edges": a node attends over every node of its graph within H bonds
 (``Adjacency.from_csr(rowptr, colidx, N, device, etype=etype)`` of ``store.adjacency(graph_ids, hops=H)``) and each

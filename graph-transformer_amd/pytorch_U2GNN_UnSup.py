@@ -17,7 +17,9 @@ Extra keyword ``attention``: "nodes" (the fork: attention over all nodes of the 
 each node over its k+1 sampled neighbours) or "graphs" (each node over the nodes of its own graph; the batch must
 be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`` / ``from_store`` build them) or
 "edges" (each node over itself and its graph neighbours; the batch must be a ``DeviceBatch`` whose ``adj`` is
-``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)``, else a ValueError).  ``hops`` = None, or H in [1, 31]
+``Adjacency.from_csr(*store.adjacency(graph_ids), N, device)`` or, assembled on the GPU from a per-dataset
+``graphs = DeviceGraphs.from_store(store, device, hops)``, what ``DeviceBatch.from_store(hb, X_dev, graphs=graphs)``
+sets; else a ValueError).  ``hops`` = None, or H in [1, 31]
 with attention="edges": attention over the H-hop neighbourhood with a learned bias per shortest-path distance, one more
 trainable parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last), as in pytorch_U2GNN_Sup.
 """

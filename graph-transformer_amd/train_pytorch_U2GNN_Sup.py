@@ -29,7 +29,7 @@ import torch.nn as nn  # noqa: E402
 torch.manual_seed(123)
 np.random.seed(123)
 
-from u2gnn_hip.cli import Run, check_world, self_launch, step_seed  # noqa: E402  (no GPU work at import)
+from u2gnn_hip.cli import Run, check_world, device_graphs, self_launch, step_seed  # noqa: E402  (no GPU work at import)
 
 parser = ArgumentParser("U2GNN", formatter_class=ArgumentDefaultsHelpFormatter, conflict_handler='resolve')
 parser.add_argument("--run_folder", default="../", help="")
@@ -59,6 +59,11 @@ parser.add_argument("--hops", default=0, type=int,
                     help="with --attention edges: each node attends over every node of its graph within this many "
                          "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
                          "scores (one more parameter, hop_bias); 0 = off, the plain adjacency")
+parser.add_argument("--adjacency", default="device", choices=["device", "host"],
+                    help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
+                         "from a per-dataset structure kept there (built once at start; a dataset whose structure "
+                         "does not fit falls back to host); host = built on the host for every batch and copied.  "
+                         "Both give the same integers, hence the same losses")
 parser.add_argument("--autograd", action="store_true", help="reference loop: autograd + torch Adam/StepLR")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
@@ -119,14 +124,21 @@ steps_per_epoch = -(-num_batches_per_epoch // run.world)
 
 
 train_X = torch.from_numpy(train_store.X).to(device)
+# --adjacency device: each store's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
+edges = args.attention == "edges"
+graphs_of = {id(s): device_graphs(s, device, args.hops, args.adjacency, log) if edges else None
+             for s in (train_store, test_store)}
 
 
 def to_device(hb, store=train_store):
+    dg = graphs_of[id(store)]
     if hb.X_concat is None:
-        b = DeviceBatch.from_store(hb, train_X, device=device)
+        b = DeviceBatch.from_store(hb, train_X, device=device, graphs=dg)
     else:
         b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
-    if args.attention == "edges":   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists), from the store
+        if dg is not None:
+            b.adj = dg.adjacency(hb.graph_ids, b.rowptr)
+    if edges and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists), from the store
         b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
     return b
 

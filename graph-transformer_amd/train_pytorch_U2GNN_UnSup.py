@@ -28,7 +28,7 @@ import torch  # noqa: E402
 torch.manual_seed(123)
 np.random.seed(123)
 
-from u2gnn_hip.cli import Run, check_world, self_launch, step_seed  # noqa: E402  (no GPU work at import)
+from u2gnn_hip.cli import Run, check_world, device_graphs, self_launch, step_seed  # noqa: E402  (no GPU work at import)
 
 parser = ArgumentParser("U2GNN", formatter_class=ArgumentDefaultsHelpFormatter, conflict_handler='resolve')
 parser.add_argument("--run_folder", default="../", help="")
@@ -60,6 +60,11 @@ parser.add_argument("--hops", default=0, type=int,
                          "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
                          "scores (one more parameter, hop_bias); 0 = off, the plain adjacency.  Not with --world_size "
                          "> 1: the unsupervised gradient exchange does not carry hop_bias yet")
+parser.add_argument("--adjacency", default="device", choices=["device", "host"],
+                    help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
+                         "from a per-dataset structure kept there (built once at start; a dataset whose structure "
+                         "does not fit falls back to host); host = built on the host for every batch and copied.  "
+                         "Both give the same integers, hence the same losses")
 parser.add_argument("--world_size", default=1, type=int,
                     help="data-parallel ranks, one per GPU (started here under torch.distributed.run unless a "
                          "launcher already set WORLD_SIZE; left at 1 under a launcher it takes WORLD_SIZE).  "
@@ -107,6 +112,8 @@ if reddit:
     feature_dim_size = 4
 store = GraphStore(graphs, reddit_tile=4 if reddit else 0)
 store_X = torch.from_numpy(store.X).to(device)
+# --adjacency device: the dataset's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
+store_graphs = device_graphs(store, device, args.hops, args.adjacency, log) if args.attention == "edges" else None
 vocab_size = int(store.node_start[-1])
 # native assembly; node features gathered on the GPU from a device-resident copy (DeviceBatch.from_store)
 batch_nodes = BatchLoader(store, args.batch_size, args.num_neighbors, with_input_y=True, gather_x=False)
@@ -139,8 +146,8 @@ def train():
         if args.max_steps and steps_done >= args.max_steps:
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
-        b = DeviceBatch.from_store(hb, store_X, device=device)
-        if args.attention == "edges":   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
+        b = DeviceBatch.from_store(hb, store_X, device=device, graphs=store_graphs)
+        if args.attention == "edges" and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
             b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]

@@ -130,6 +130,13 @@ class CsrAttn(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in ("rowptr", "colidx", "t_rowptr", "t_src", "t_eid")] + [("nnz", c_int64)]
 
 
+class GraphStructure(ctypes.Structure):
+    """u2gnn_graph_structure: the device arrays of a dataset's per-graph adjacency pieces (pattern.DeviceGraphs owns
+    them)."""
+    _fields_ = ([(k, c_void_p) for k in ("node_start", "ent_start", "rowptr", "t_rowptr", "col", "t_src", "t_eid",
+                                         "etype")] + [(k, c_int64) for k in ("G", "V", "E")])
+
+
 _TAIL_PTRS = ("W_o", "b_o", "n1_w", "n1_b", "W1", "b1", "W2", "b2", "n2_w", "n2_b", "O", "X", "Z1", "X1", "mean1",
               "rstd1", "Hd", "Z2", "X2", "mean2", "rstd2", "dX2", "dX1", "dF", "dH", "dX", "dA", "dO", "delta")
 
@@ -192,6 +199,8 @@ _HIP_SIGS = {
     "u2gnn_bias_expand": ([VP, I32, I32, VP, I64, VP, I64, VP], c_int32),
     "u2gnn_bias_table_grad_ws_floats": ([I32, I32, I64], I64),
     "u2gnn_bias_table_grad": ([VP, I64, I32, I32, VP, I64, VP, VP, I64, VP], c_int32),
+    "u2gnn_adjacency_assemble": ([POINTER(GraphStructure), VP, VP, VP, I32, I64, I64, VP, VP, VP, VP, VP, VP, VP, VP],
+                                 c_int32),
     "u2gnn_layer_fwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
                               VP, I32, POINTER(CsrAttn), VP, VP], c_int32),
     "u2gnn_layer_bwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,

@@ -249,6 +249,9 @@ class PinnedSlot:
         self.gnode = torch.empty(max_rows, dtype=torch.int64, pin_memory=True)
         self.offsets = torch.empty(max_graphs + 1, dtype=torch.int64, pin_memory=True)
         self.labels = torch.empty(max_graphs, dtype=torch.int64, pin_memory=True)
+        # DeviceBatch.from_store(..., graphs=): the batch's graph ids and entry offsets (pattern.DeviceGraphs.plan)
+        self.gid = torch.empty(max_graphs, dtype=torch.int64, pin_memory=True)
+        self.ent_off = torch.empty(max_graphs + 1, dtype=torch.int64, pin_memory=True)
         self.event = None
 
     def wait(self):

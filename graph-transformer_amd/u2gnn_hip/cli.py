@@ -51,6 +51,20 @@ def check_world(run_world: int, flag: int) -> None:
         raise SystemExit(f"WORLD_SIZE={run_world} but --world_size {flag}")
 
 
+def device_graphs(store, device, hops, choice: str, log=print, max_bytes: int = 8 << 30):
+    """--adjacency of the CLIs (with --attention edges): ``device`` = the store's pattern.DeviceGraphs, built once, from
+    which every batch's adjacency is assembled on the GPU; ``host`` = None, and the caller builds each batch's with
+    Adjacency.from_store.  A structure that cannot be kept (larger than max_bytes) logs one line and gives None."""
+    if choice != "device":
+        return None
+    from .pattern import DeviceGraphs
+    try:
+        return DeviceGraphs.from_store(store, device, hops=hops or None, max_bytes=max_bytes)
+    except ValueError as e:
+        log(f"--adjacency device: {e}; building each batch's adjacency on the host")
+        return None
+
+
 _MASK = (1 << 64) - 1
 
 

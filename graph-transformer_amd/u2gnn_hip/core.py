@@ -24,7 +24,8 @@ from .engine import deep_wgrad as engine_deep_wgrad
 from .engine import (SITE_ATTN, SITE_DROP1, SITE_DROP2, SITE_DROPFF, SITE_HEAD, Dims, LayerParams, PackedLayer,
                      OffPath, encoder_layer_backward, encoder_layer_forward, rup, side_stream_pays, site_seed)
 # (Adjacency, check_hops, ATTENTION_MODES: re-exported, the models, tools and tests import them from here)
-from .pattern import ATTENTION_MODES, NODES, Adjacency, AttnPattern, check_attention, check_hops  # noqa: F401
+from .pattern import (ATTENTION_MODES, NODES, Adjacency, AttnPattern, DeviceGraphs, check_attention,  # noqa: F401
+                      check_hops)
 
 
 _IOTA = {}
@@ -71,8 +72,8 @@ class DeviceBatch:
     # what attention="graphs" needs, since its segments are rowptr.  from_offsets / from_store build such batches;
     # from_reference_inputs checks its graph_pool
     rows_contiguous: bool = False
-    # the rows' attention pattern (attention="edges"): Adjacency.from_csr(*store.adjacency(graph_ids), N, device);
-    # the other modes never read it
+    # the rows' attention pattern (attention="edges"): Adjacency.from_csr(*store.adjacency(graph_ids), N, device), or
+    # the same arrays assembled on the GPU (from_store(..., graphs=DeviceGraphs)); the other modes never read it
     adj: Optional[Adjacency] = None
 
     def __post_init__(self):
@@ -106,17 +107,25 @@ class DeviceBatch:
                            rows_contiguous=True)
 
     @staticmethod
-    def from_store(hb, X_dev: torch.Tensor, device="cuda"):
+    def from_store(hb, X_dev: torch.Tensor, device="cuda", graphs=None):
         """A natively assembled batch (GraphStore.assemble(..., gather_x=False)) -> HBM: input_x, offsets
         and the rows' dataset node ids cross PCIe asynchronously from page-locked buffers (~0.7 MB at
         C4 instead of the 7 MB X_concat; BatchLoader assembles straight into a ring of them);
         X_concat is gathered on the GPU from the dataset's device-resident features X_dev [V, d]
-        (u2gnn_gather_rows).  No host synchronisation."""
+        (u2gnn_gather_rows).  No host synchronisation.
+        graphs: the store's pattern.DeviceGraphs -- the batch also gets its adjacency (``adj``, attention="edges"),
+        assembled on the GPU from the device-resident structure: the graph ids and entry offsets travel with the
+        arrays above, the row offsets are the batch's own, and the kernel runs beside the feature gather."""
         from . import kernels as K
         dev = torch.device(device)
         N, B = int(hb.offsets[-1]), len(hb.offsets) - 1
         slot = getattr(hb, "pinned", None)
         _check_range_host(hb.input_x, N)
+        plan = None
+        if graphs is not None:   # host tables only: the ids checked, the entry offsets, nnz and n_types
+            plan = graphs.plan(hb.graph_ids)
+            if plan[3] != N or len(plan[0]) != B:
+                raise ValueError(f"graphs: the structure gives the batch {plan[3]} rows, the batch has {N}")
         if slot is not None and dev.type == "cuda":
             # the batch's transfers and its feature gather run on a copy stream, so the next batch
             # crosses PCIe while the current step computes; the compute stream waits on one event
@@ -127,6 +136,9 @@ class DeviceBatch:
                 h2d = lambda t: t.to(dev, non_blocking=True)  # noqa: E731
                 ix = h2d(slot.ix[:N * k1]).view(N, k1)
                 gnode, off, lab = h2d(slot.gnode[:N]), h2d(slot.offsets[:B + 1]), h2d(slot.labels[:B])
+                if plan is not None:
+                    slot.gid.numpy()[:B], slot.ent_off.numpy()[:B + 1] = plan[0], plan[2]
+                    gid, ent_off = h2d(slot.gid[:B]), h2d(slot.ent_off[:B + 1])
                 slot.event = torch.cuda.Event()
                 slot.event.record()
                 d = X_dev.shape[1]
@@ -134,14 +146,19 @@ class DeviceBatch:
                 if N:
                     K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
                 err = torch.zeros(1, device=dev, dtype=torch.int32)
+                adj = None if plan is None else graphs.launch(gid, off, ent_off, *plan[3:])
             ready = torch.cuda.Event()
             ready.record(cs)
             main.wait_event(ready)
-            for t in (ix, gnode, off, lab, X, err):   # allocated on the copy stream, used on the compute one
+            used = [ix, gnode, off, lab, X, err]   # allocated on the copy stream, used on the compute one
+            if adj is not None:   # (the adjacency's five arrays are views of one buffer, rowptr its start)
+                used += [gid, ent_off, adj.rowptr] + ([adj.etype] if adj.etype is not None else [])
+            for t in used:
                 t.record_stream(main)
             iy = gnode if hb.input_y is not None else None
             colidx, vals = _pool_iota(N, dev)
-            return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True, rows_contiguous=True)
+            return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True, rows_contiguous=True,
+                               adj=adj)
         if slot is not None:
             k1 = hb.input_x.shape[1]
             h2d = lambda t: t.to(dev, non_blocking=True)  # noqa: E731
@@ -160,7 +177,8 @@ class DeviceBatch:
         if N:
             K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
         colidx, vals = _pool_iota(N, dev)
-        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True)
+        adj = None if graphs is None else graphs.adjacency(hb.graph_ids, off)
+        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True, adj=adj)
 
     @staticmethod
     def from_reference_inputs(input_x, graph_pool, X_concat, labels=None):

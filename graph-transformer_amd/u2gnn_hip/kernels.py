@@ -387,6 +387,27 @@ def bias_table_grad(dbias, etype, dtables):
           "u2gnn_bias_table_grad")
 
 
+def adjacency_assemble(structure, gid, row_off, ent_off, N, nnz, rowptr, colidx, t_rowptr, t_src, t_eid, etype, err):
+    """A batch's adjacency arrays from a dataset's per-graph pieces (structure: _lib.GraphStructure of device arrays,
+    pattern.DeviceGraphs): gid int64 [B], row_off / ent_off int64 [B+1] on the device; rowptr / t_rowptr (int64, at
+    least N + 1) and colidx / t_src / t_eid (int64, at least nnz) receive exactly N + 1 and nnz values, etype (int32,
+    at least nnz, or None) the entry types; err int32 [1] is set to 1 when a slot or an index is out of range (such
+    entries are written as -1).  One launch on the current stream; nothing is read back."""
+    i64, outs = (gid, row_off, ent_off, rowptr, colidx, t_rowptr, t_src, t_eid), (rowptr, colidx, t_rowptr, t_src, t_eid)
+    _dev(*i64, etype, err)
+    B = gid.numel()
+    if any(t.dtype != torch.int64 or not t.is_contiguous() for t in i64) or err.dtype != torch.int32 or (
+            etype is not None and (etype.dtype != torch.int32 or not etype.is_contiguous())):
+        raise _lib.U2GNNNativeError("adjacency_assemble: contiguous int64 index arrays, int32 etype and err")
+    if row_off.numel() != B + 1 or ent_off.numel() != B + 1 or err.numel() < 1:
+        raise _lib.U2GNNNativeError("adjacency_assemble: row_off and ent_off hold one value per graph and the total")
+    if any(t.numel() < n for t, n in zip(outs + (etype,), (N + 1, nnz, N + 1, nnz, nnz, nnz)) if t is not None):
+        raise _lib.U2GNNNativeError("adjacency_assemble: the outputs hold N + 1 row pointers and nnz entries")
+    check(hip_lib().u2gnn_adjacency_assemble(ctypes.byref(structure), _p(gid), _p(row_off), _p(ent_off), int(B), int(N),
+                                             int(nnz), _p(rowptr), _p(colidx), _p(t_rowptr), _p(t_src), _p(t_eid),
+                                             _p(etype), _p(err), _s()), "u2gnn_adjacency_assemble")
+
+
 def rowdot(A, lda, B, ldb, out, rows, cols):
     _dev(A, B, out)
     check(hip_lib().u2gnn_rowdot(_p(A), int(lda), _p(B), int(ldb), _p(out), int(rows), int(cols), _s()),

@@ -95,6 +95,176 @@ class Adjacency:
         return self._c
 
 
+class DeviceGraphs:
+    """A dataset's adjacency, kept on the device as per-graph pieces, so that a batch's Adjacency is assembled there
+    (u2gnn_adjacency_assemble) instead of being built on the host and copied for every batch.
+
+    A batch's adjacency is block-diagonal: graph g's columns lie in its own row range and its entries are contiguous
+    in entry order, so the stable sort by column that gives the transpose groups by graph first and keeps the entry
+    order inside each graph.  Everything ``Adjacency.from_csr`` computes for a batch is therefore the concatenation
+    of its graphs' pieces plus two offsets per graph (the graph's first row and first entry in the batch).  The
+    pieces, computed once for all G graphs (V nodes, E entries):
+
+    * ``node_start``, ``ent_start`` int64 [G+1]: graph g's nodes and entries in the dataset's numbering;
+    * ``rowptr``, ``t_rowptr`` int64 [V+1]: the first entry of each node's list / transposed list;
+    * ``col``, ``t_src``, ``t_eid`` int32 [E]: column, source row and entry id inside the graph;
+    * ``etype`` uint8 [E], only with ``hops``: the entry's distance.
+
+    The host keeps each graph's node count, entry count and largest distance: a batch's N, nnz and n_types come from
+    them, never from the device.  ``adjacency(ids)`` equals ``Adjacency.from_csr(*store.adjacency(ids, hops), N,
+    device)`` integer for integer; ``assemble_numpy(ids)`` is the numpy statement of the same assembly."""
+    ARRAYS = ("node_start", "ent_start", "rowptr", "t_rowptr", "col", "t_src", "t_eid", "etype")
+
+    def __init__(self, host: dict, hops, device):
+        self.hops, self.device = hops, torch.device(device)
+        self.host = host                                           # the numpy arrays (etype None without hops)
+        self.G, self.V, self.E = len(host["node_start"]) - 1, int(host["node_start"][-1]), int(host["ent_start"][-1])
+        self.n_nodes = np.diff(host["node_start"])
+        self.n_entries = np.diff(host["ent_start"])
+        et = host["etype"]
+        if et is None or not self.E:
+            self.max_dist = np.zeros(self.G, dtype=np.int64)
+        else:   # per graph; a graph without entries (no nodes) keeps 0
+            self.max_dist = np.maximum.reduceat(et, np.minimum(host["ent_start"][:-1], self.E - 1)).astype(np.int64)
+            self.max_dist[self.n_entries == 0] = 0
+        self.dev = {k: None if host[k] is None else torch.from_numpy(host[k]).to(self.device) for k in self.ARRAYS}
+        self.err = torch.zeros(1, device=self.device, dtype=torch.int32)   # set by the kernel, never on checked ids
+        if self.device.type == "cuda":   # built once; batches are assembled on other streams (DeviceBatch.from_store)
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c = None
+
+    @staticmethod
+    def nbytes(G: int, V: int, E: int, hops) -> int:
+        """The size of the dataset-wide arrays."""
+        return 16 * (G + 1) + 16 * (V + 1) + (13 if hops else 12) * E
+
+    @staticmethod
+    def from_store(store, device="cuda", hops=None, max_bytes=8 << 30) -> "DeviceGraphs":
+        """The structure of all of ``store``'s graphs (any store with ``n_nodes`` and ``adjacency(ids, hops=)``), built
+        once on the host from one ``store.adjacency(range(G), hops)`` and its transpose (as ``Adjacency.from_csr``
+        takes it), rewritten into each graph's own numbering, then moved to ``device``.  hops None or 0: off.
+        ValueError: ``hops`` outside [1, 31]; a graph with 2^31 or more nodes or entries; arrays larger than
+        ``max_bytes`` (known from the counts, before anything is allocated on or copied to the device)."""
+        from .batching import check_hops_range
+        hops = check_hops_range(hops) if hops else None
+        n = np.asarray(store.n_nodes, dtype=np.int64)
+        G, V = len(n), int(n.sum())
+        if G < 1 or V < 1:
+            raise ValueError("device graphs: the store holds no nodes")
+        limit = lambda E: DeviceGraphs._check_size(G, V, E, hops, max_bytes)  # noqa: E731
+        limit(V)                                                   # every node lists itself: E >= V
+        if n.max() >= 1 << 31:
+            raise ValueError("device graphs: a graph with 2^31 or more nodes")
+        csr = store.adjacency(np.arange(G, dtype=np.int64), hops=hops)
+        rp = np.ascontiguousarray(csr[0], dtype=np.int64)
+        ci = np.ascontiguousarray(csr[1], dtype=np.int64)
+        E = int(ci.shape[0])
+        limit(E)
+        node_start = np.zeros(G + 1, dtype=np.int64)
+        np.cumsum(n, out=node_start[1:])
+        ent_start = np.ascontiguousarray(rp[node_start])
+        if (np.diff(ent_start) >= 1 << 31).any():
+            raise ValueError("device graphs: a graph with 2^31 or more entries")
+        # the whole dataset's transpose, exactly as Adjacency.from_csr takes a batch's
+        order = np.argsort(ci, kind="stable")
+        t_rowptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(ci, minlength=V), out=t_rowptr[1:])
+        rows = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+        # into each graph's numbering: entry p and transposed entry p both belong to the graph that owns position p
+        # (checked: a column inside its graph's nodes, a transposed entry's id inside its graph's entries)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        seg = np.diff(ent_start)
+        first = np.repeat(node_start[:-1], seg)
+        col, t_src = ci - first, i32(rows[order] - first)
+        ok = not E or (col.min() >= 0 and bool((col < np.repeat(n, seg)).all()))
+        del first, rows
+        col = i32(col)
+        t_eid = order - np.repeat(ent_start[:-1], seg)
+        if not ok or (E and (t_eid.min() < 0 or bool((t_eid >= np.repeat(seg, seg)).any()))):
+            raise ValueError("device graphs: the store's adjacency is not block-diagonal by graph")
+        host = {"node_start": node_start, "ent_start": ent_start, "rowptr": rp, "t_rowptr": t_rowptr, "col": col,
+                "t_src": t_src, "t_eid": i32(t_eid),
+                "etype": np.ascontiguousarray(csr[2], dtype=np.uint8) if hops else None}
+        return DeviceGraphs(host, hops, device)
+
+    @staticmethod
+    def _check_size(G, V, E, hops, max_bytes):
+        need = DeviceGraphs.nbytes(G, V, E, hops)
+        if need > max_bytes:
+            raise ValueError(f"device graphs: the arrays need at least {need} bytes, more than max_bytes = {max_bytes}")
+
+    def c_struct(self):
+        """The u2gnn_graph_structure of the device arrays (kept alive with them)."""
+        if self._c is None:
+            from ._lib import GraphStructure
+            self._c = GraphStructure(*[None if self.dev[k] is None else self.dev[k].data_ptr() for k in self.ARRAYS],
+                                     self.G, self.V, self.E)
+        return self._c
+
+    def plan(self, graph_ids):
+        """(ids, row_off, ent_off, N, nnz, n_types) of the batch ``graph_ids``, from the host tables alone: int64
+        arrays [B], [B+1], [B+1].  ValueError for an empty batch or an id outside [0, G)."""
+        ids = np.ascontiguousarray(graph_ids, dtype=np.int64).reshape(-1)
+        if ids.shape[0] < 1 or ids.min() < 0 or ids.max() >= self.G:
+            raise ValueError(f"device graphs: a batch of at least one graph id in [0, {self.G})")
+        row_off, ent_off = np.zeros(len(ids) + 1, dtype=np.int64), np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum(self.n_nodes[ids], out=row_off[1:])
+        np.cumsum(self.n_entries[ids], out=ent_off[1:])
+        n_types = int(self.max_dist[ids].max()) + 1 if self.hops and ent_off[-1] else 0
+        return ids, row_off, ent_off, int(row_off[-1]), int(ent_off[-1]), n_types
+
+    def assemble_numpy(self, graph_ids):
+        """(rowptr, colidx, t_rowptr, t_src, t_eid, etype) of the batch as host numpy arrays (int64; etype int32, None
+        without hops): what the kernel writes, and what ``Adjacency.from_csr`` builds from the batch's CSR."""
+        h = self.host
+        ids, row_off, ent_off, N, nnz, _ = self.plan(graph_ids)
+        slot_r = np.repeat(np.arange(len(ids)), self.n_nodes[ids])            # the slot of each batch row / entry
+        slot_e = np.repeat(np.arange(len(ids)), self.n_entries[ids])
+        v = h["node_start"][ids][slot_r] + np.arange(N, dtype=np.int64) - row_off[slot_r]
+        s = h["ent_start"][ids][slot_e] + np.arange(nnz, dtype=np.int64) - ent_off[slot_e]
+        shift = (ent_off[:-1] - h["ent_start"][ids])[slot_r]
+        rowptr, t_rowptr = np.full(N + 1, nnz, dtype=np.int64), np.full(N + 1, nnz, dtype=np.int64)
+        rowptr[:N], t_rowptr[:N] = h["rowptr"][v] + shift, h["t_rowptr"][v] + shift
+        ro, eo = row_off[slot_e], ent_off[slot_e]
+        etype = None if h["etype"] is None else h["etype"][s].astype(np.int32)
+        return rowptr, h["col"][s] + ro, t_rowptr, h["t_src"][s] + ro, h["t_eid"][s] + eo, etype
+
+    def launch(self, gid, row_off, ent_off, N: int, nnz: int, n_types: int) -> Adjacency:
+        """The batch's Adjacency from device int64 ``gid`` [B], ``row_off`` / ``ent_off`` [B+1] (``plan``'s arrays):
+        allocates the outputs and launches u2gnn_adjacency_assemble on the current stream."""
+        from . import kernels as K
+        if nnz < 1:
+            raise ValueError("device graphs: a batch without entries")
+        np1 = N + 2 - N % 2                                        # N + 1 row pointers, the next array 16-byte aligned
+        buf = torch.empty(2 * np1 + 3 * nnz, device=gid.device, dtype=torch.int64)
+        rowptr, t_rowptr = buf[:N + 1], buf[np1:np1 + N + 1]
+        colidx, t_src, t_eid = (buf[2 * np1 + i * nnz:2 * np1 + (i + 1) * nnz] for i in range(3))
+        etype = torch.empty(nnz, device=gid.device, dtype=torch.int32) if self.hops else None
+        K.adjacency_assemble(self.c_struct(), gid, row_off, ent_off, N, nnz, rowptr, colidx, t_rowptr, t_src, t_eid,
+                             etype, self.err)
+        return Adjacency(N, rowptr, colidx, t_rowptr, t_src, t_eid, etype, n_types)
+
+    def adjacency(self, graph_ids, row_off_dev=None) -> Adjacency:
+        """The Adjacency of the batch ``graph_ids`` (in that order), assembled on the device: the ids are checked on
+        the host (ValueError outside [0, G)), ids and offsets leave from page-locked memory without blocking, the
+        kernel runs on the current stream.  row_off_dev: the batch's row offsets when they are on the device already
+        (DeviceBatch.rowptr of a batch built from offsets)."""
+        ids, row_off, ent_off, N, nnz, n_types = self.plan(graph_ids)
+        B = len(ids)
+        pin = self.device.type == "cuda"
+        stage = torch.empty(3 * B + 2, dtype=torch.int64, pin_memory=pin)   # the caching host allocator keeps a block
+        h = stage.numpy()                                                  # until the copy that reads it is done
+        h[:B], h[B:2 * B + 1], h[2 * B + 1:] = ids, ent_off, row_off
+        n_send = 2 * B + 1 if row_off_dev is not None else 3 * B + 2
+        d = stage[:n_send].to(self.device, non_blocking=True)
+        return self.launch(d[:B], d[2 * B + 1:] if row_off_dev is None else row_off_dev, d[B:2 * B + 1], N, nnz, n_types)
+
+    def check_indices(self):
+        """IndexError if a launch met a slot or an index out of range (host sync)."""
+        if int(self.err.item()):
+            raise IndexError("device graphs: a graph id or an index out of range reached the kernel")
+
+
 class AttnPattern:
     """The rows one encoder layer's rows attend over; an immutable value of exactly one kind:
 

@@ -625,6 +625,46 @@ int64_t u2gnn_bias_table_grad_ws_floats(int32_t R, int32_t n_types, int64_t nnz)
 int u2gnn_bias_table_grad(const float *dbias, int64_t ld, int32_t R, int32_t n_types, const int32_t *etype, int64_t nnz,
                           float *dtables, float *ws, int64_t ws_floats, void *stream);
 
+/* ---- a batch's u2gnn_csr_attn arrays assembled on the device from a per-dataset structure (ABI 19 grew by this
+ * entry point, nothing else changed).  A batch's adjacency is block-diagonal, so everything the host builder
+ * (u2gnn_hip.pattern.Adjacency.from_csr) computes for a batch -- rowptr, colidx, the transpose by a stable sort of
+ * the columns, the entry types -- is the concatenation of its graphs' pieces plus two offsets per graph.  The pieces
+ * are computed once per dataset (u2gnn_hip.pattern.DeviceGraphs) and stay on the device:
+ *   node_start, ent_start [G+1]: graph g owns the dataset nodes node_start[g] .. node_start[g+1]-1 and the entries
+ *     ent_start[g] .. ent_start[g+1]-1 (of the lists and of the transposed lists alike);
+ *   rowptr, t_rowptr [V+1]: the first entry of node v's list / transposed list, as a dataset-wide entry index;
+ *   col, t_src, t_eid [E]: an entry's column, and a transposed entry's source row and entry id, each inside its own
+ *     graph (a node as node - node_start[g], an entry as entry - ent_start[g]);
+ *   etype [E] or NULL: an entry's type (the hop distance).
+ * u2gnn_adjacency_assemble: the batch of the B graphs gid[b] (device int64 [B]) whose rows start at row_off[b] and
+ * whose entries start at ent_off[b] (device int64 [B+1] each, ending at N and nnz).  Batch row r of slot b is the
+ * dataset node v = node_start[gid[b]] + r - row_off[b]:
+ *   rowptr[r] = ent_off[b] + S.rowptr[v] - ent_start[gid[b]], t_rowptr likewise, rowptr[N] = t_rowptr[N] = nnz;
+ * batch entry e of slot b reads the source index s = ent_start[gid[b]] + e - ent_off[b]:
+ *   colidx[e] = col[s] + row_off[b], t_src[e] = t_src[s] + row_off[b], t_eid[e] = t_eid[s] + ent_off[b],
+ *   etype[e] = etype[s] (int32; etype == NULL: not written, and it must be NULL when the structure has none).
+ * rowptr, t_rowptr: int64 [N+1]; colidx, t_src, t_eid: int64 [nnz]; nothing past them is written.  One launch,
+ * coalesced loads and stores, a block's first slot found by one binary search over ent_off / row_off, no atomics:
+ * bit-identical from run to run.  Nothing returns to the host.
+ * Any content is memory-safe: every read of S is bounds-checked.  An entry whose slot has a gid outside [0, G) or
+ * whose source index lies outside [0, E) gets colidx = t_src = t_eid = -1 (and etype 0) -- the attention kernels
+ * skip such entries -- and *err (device int32) is set to 1; a row whose gid or node is out of range sets *err too;
+ * every rowptr / t_rowptr value is clamped to [0, nnz].  *err is only ever set, never cleared.
+ * Null pointers (S, its members but etype, gid, row_off, ent_off, the five outputs, err), etype without S->etype,
+ * G, V, E, B, N or nnz < 1: U2GNN_E_ARG before anything is launched; more than 2^31 - 1 blocks of 1024 elements:
+ * U2GNN_E_SHAPE. */
+typedef struct u2gnn_graph_structure {
+    const int64_t *node_start, *ent_start;   /* [G+1] */
+    const int64_t *rowptr, *t_rowptr;        /* [V+1] */
+    const int32_t *col, *t_src, *t_eid;      /* [E] */
+    const uint8_t *etype;                    /* [E] or NULL */
+    int64_t G, V, E;                         /* graphs, nodes, entries of the dataset */
+} u2gnn_graph_structure;
+int u2gnn_adjacency_assemble(const u2gnn_graph_structure *S, const int64_t *gid, const int64_t *row_off,
+                             const int64_t *ent_off, int32_t B, int64_t N, int64_t nnz, int64_t *rowptr,
+                             int64_t *colidx, int64_t *t_rowptr, int64_t *t_src, int64_t *t_eid, int32_t *etype,
+                             int32_t *err, void *stream);
+
 /* ---- a3: one encoder layer (TransformerEncoderLayer(d, nhead=1, ff, dropout), post-LN, slot-0
  * rows) issued natively: forward and backward of pytorch_U2GNN_Sup.py:19-21,35 /
  * pytorch_U2GNN_UnSup.py:37-40,57, launch-for-launch the sequence of u2gnn_hip/engine.py.

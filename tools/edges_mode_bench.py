@@ -14,8 +14,12 @@ beside the three modes in the same rotation, and per batch and H: nnz, the CSR f
 without a bias and with a zero bias (the BIAS instantiations at equal arithmetic), and the u2gnn_bias_expand and
 u2gnn_bias_table_grad launches for the step's T tables.  --settings picks the settings to run.
 
+--pipeline times something else (and nothing of the above): edges-mode steps on fresh batches from a BatchLoader over
+a GraphStore, with the adjacency resident, built on the host per batch, or assembled on the GPU per batch from the
+store's DeviceGraphs, and the assemble kernel alone (pipeline() below); with --hops also per H.
+
 Prints one JSON line.  Usage: python tools/edges_mode_bench.py [--steps 24] [--warmup 5] [--batches 4] [--hops 1,2]
-[--settings c4,mutag]"""
+[--settings c4,mutag] [--pipeline]"""
 import argparse
 import json
 import math
@@ -170,8 +174,125 @@ def setting(name, store, C, batch_size, k, args):
     return out
 
 
+def assemble_figures(dg, ids):
+    """u2gnn_adjacency_assemble alone on one batch: device time per launch (REPS launches in one HIP graph, events
+    around its replay) and the bytes it moves -- per entry three int32 and, with hops, one byte read, three int64 and
+    one int32 written; per row two int64 read and two written."""
+    ids, row_off, ent_off, N, nnz, n_types = dg.plan(ids)
+    dev = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    gid, ro, eo = dev(ids), dev(row_off), dev(ent_off)
+    out = [torch.empty(n, device="cuda", dtype=torch.int64) for n in (N + 1, nnz, N + 1, nnz, nnz)]
+    et = torch.empty(nnz, device="cuda", dtype=torch.int32) if dg.hops else None
+    us = graph_time_us(lambda: K.adjacency_assemble(dg.c_struct(), gid, ro, eo, N, nnz, *out, et, dg.err))
+    moved = nnz * ((13 + 28) if dg.hops else (12 + 24)) + (N + 1) * 32
+    return {"N": N, "nnz": nnz, "assemble_us": round(us, 2), "moved_mb": round(moved / 1e6, 3),
+            "gbs": round(moved / us / 1e3, 1)}
+
+
+def pipeline(name, store, C, batch_size, k, args, hops=None):
+    """attention="edges" steps on FRESH batches from a BatchLoader over a GraphStore (native assembly into page-locked
+    slots, DeviceBatch.from_store), three variants in rotating blocks of one process, one trainer:
+
+      resident: --batches batches built up front and replayed (what the step figures above time);
+      host:     every step draws a batch and builds its adjacency on the host (Adjacency.from_store) -- the CLIs'
+                --adjacency host;
+      device:   every step draws a batch and DeviceBatch.from_store(..., graphs=) assembles its adjacency on the GPU
+                from the store's DeviceGraphs -- the CLIs' --adjacency device.
+
+    A block is --block steps between two synchronisations, timed on the host clock (the host work is the subject);
+    per variant the median of its blocks' per-step times.  pass: device no slower than host by more than the spread
+    (max - min) of host's own blocks.  The structure's one-off build is timed apart."""
+    import time
+    from pytorch_U2GNN_Sup import TransformerU2GNN
+    from u2gnn_hip.batching import BatchLoader
+    from u2gnn_hip.core import Adjacency, DeviceBatch
+    from u2gnn_hip.pattern import DeviceGraphs
+    from u2gnn_hip.train import SupTrainer
+    T, ff = 4, 1024
+    t0 = time.perf_counter()
+    dg = DeviceGraphs.from_store(store, "cuda", hops=hops)
+    build_s = time.perf_counter() - t0
+    X_dev = torch.from_numpy(store.X).cuda()
+    np.random.seed(123)
+    loader = BatchLoader(store, batch_size, k, gather_x=False)
+    resident = [DeviceBatch.from_store(loader(), X_dev, "cuda", graphs=dg) for _ in range(args.batches)]
+    torch.manual_seed(123)
+    m = TransformerU2GNN(store.d, ff, C, T, 0.5, 1, precision=args.precision, attention="edges", hops=hops).cuda().train()
+    tr = SupTrainer(m, lr=5e-4, max_norm=0.5, seed=123)
+    count = [0]
+
+    def feed_resident():
+        count[0] += 1
+        return resident[count[0] % len(resident)]
+
+    def feed_host():
+        hb = loader()
+        b = DeviceBatch.from_store(hb, X_dev, "cuda")
+        b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, "cuda", hops)
+        return b
+
+    def feed_device():
+        return DeviceBatch.from_store(loader(), X_dev, "cuda", graphs=dg)
+    feeds = {"resident": feed_resident, "host": feed_host, "device": feed_device}
+    names = tuple(feeds)
+    for f in feeds.values():
+        for _ in range(args.warmup):
+            tr.step(f())
+    torch.cuda.synchronize()
+    blocks = {n: [] for n in names}
+    done, blk = 0, 0
+    while done < args.steps:
+        r = blk % len(names)
+        n = min(args.block, args.steps - done)
+        for v in names[r:] + names[:r]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step(feeds[v]())
+            torch.cuda.synchronize()
+            blocks[v].append((time.perf_counter() - t0) * 1e3 / n)
+        done += n
+        blk += 1
+    med = {v: statistics.median(t) for v, t in blocks.items()}
+    spread = max(blocks["host"]) - min(blocks["host"])
+    dg.check_indices()
+    return {"setting": f"{name}: bs {batch_size}, k {k}, d {store.d}, T {T}, ff {ff}, {args.precision}, hops {hops}, "
+                       f"fresh batches, {args.steps} steps per variant in rotating blocks of {args.block}, host clock",
+            "structure": {"graphs": dg.G, "nodes": dg.V, "entries": dg.E, "mb": round(dg.nbytes(dg.G, dg.V, dg.E, hops) / 1e6, 2),
+                          "build_s": round(build_s, 3)},
+            "step_ms": {v: round(t, 4) for v, t in med.items()},
+            "block_ms_min_max": {v: [round(min(t), 4), round(max(t), 4)] for v, t in blocks.items()},
+            "device_over_resident": round(med["device"] / med["resident"], 4),
+            "host_over_resident": round(med["host"] / med["resident"], 4),
+            "host_block_spread_ms": round(spread, 4),
+            "pass": bool(med["device"] <= med["host"] + spread),
+            "assemble": assemble_figures(dg, loader.rng.permutation(dg.G)[:batch_size])}
+
+
+def main_pipeline(args, which):
+    import util
+    from u2gnn_hip.batching import GraphStore
+    from u2gnn_hip.synthetic import as_graph_store, collab_like
+    stores = {}
+    if "mutag" in which:
+        graphs, C = util.load_data("MUTAG", False)
+        stores["mutag"] = ("MUTAG", GraphStore(graphs), C)
+    if "c4" in which:
+        stores["c4"] = ("C4 synthetic as a GraphStore", as_graph_store(collab_like(seed=0)), 3)
+    out = {}
+    for H in [None] + args.hops:
+        res = out["pipeline" if H is None else f"pipeline_h{H}"] = {}
+        for key, (name, store, C) in stores.items():
+            res[key] = pipeline(name, store, C, 64, 16, args, H)
+            print(f"{key} hops {H}: {res[key]['step_ms']}", file=sys.stderr, flush=True)   # progress; the JSON is the result
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pipeline", action="store_true",
+                    help="instead: time edges-mode steps on fresh batches -- resident, host-built and device-built "
+                         "adjacency -- and the assemble kernel alone (see pipeline())")
     ap.add_argument("--steps", type=int, default=24, help="timed steps per mode (>= 20)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", type=int, default=4)
@@ -183,6 +304,8 @@ def main():
     args.hops = [int(h) for h in args.hops.split(",") if h]
     which = args.settings.split(",")
     assert torch.cuda.is_available(), "needs an MI355X: a timing without one would mean nothing"
+    if args.pipeline:
+        return main_pipeline(args, which)
     import util
     from u2gnn_hip.batching import GraphStore
     from u2gnn_hip.synthetic import collab_like
