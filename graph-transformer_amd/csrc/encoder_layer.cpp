@@ -65,17 +65,24 @@ struct Dims {
     // both caller-owned, null: none
     const float *csr_bias = nullptr;
     float *csr_dbias = nullptr;
+    // the segments' per-pair additive bias (u2gnn_layer_*_segb): n_pairs device floats, segment g's pairs from
+    // pair_off[g] (device), and where the backward leaves dL/dbias; caller-owned, null: none
+    const int64_t *pair_off = nullptr;
+    int64_t n_pairs = 0;
+    const float *seg_bias = nullptr;
+    float *seg_dbias = nullptr;
     Attn attn;   // set by make_dims; meaningful once pattern_ok has passed the pattern
 };
 
 // The attention pattern of a call (n_seg row segments, a CSR of nnz entries, or neither: the node-axis or window
 // layer).  Segments: offsets and count, both or neither.  CSR: none, or a complete one with at least one entry.  Never
 // the two together, and neither with window mode.  A bias only with a CSR, its gradient only with the bias.  The planning form (u2gnn_layer_sizes_*) has counts only and no
-// pointers.
+// pointers.  A per-pair bias only with segments, its pair offsets and at least one pair; its gradient only with it.
 bool pattern_ok(const Dims &D, bool plan) {
     const bool segs = D.seg || D.n_seg, csr = D.csr || D.csr_nnz;
     if (D.n_seg < 0 || D.csr_nnz < 0 || (segs && csr) || ((segs || csr) && D.window != 0)) return false;
     if ((D.csr_bias && !csr) || (D.csr_dbias && !D.csr_bias)) return false;
+    if ((D.seg_bias && !(segs && D.pair_off && D.n_pairs >= 1)) || (D.seg_dbias && !D.seg_bias)) return false;
     if (plan) return true;
     if (segs && !(D.seg && D.n_seg >= 1)) return false;
     const u2gnn_csr_attn *A = D.csr;
@@ -624,8 +631,8 @@ int layer_fwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         break;
     case Attn::segments:
         if (!plan)
-            U2GNN_TRY(u2gnn_segment_attn_fwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dp, c.stats, pd, s->attn,
-                                             N, Np, st));
+            U2GNN_TRY(u2gnn_segment_attn_fwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, D.pair_off, D.n_pairs,
+                                                  D.seg_bias, c.O, dp, c.stats, pd, s->attn, N, Np, st));
         break;
     case Attn::csr:
         if (!plan)
@@ -847,8 +854,9 @@ int layer_bwd(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seed
         // delta, dQ over query tiles, then dK, dV over key tiles (P recomputed from the statistics)
         float *seg_delta = W.take<float>(Np);
         if (!plan)
-            U2GNN_TRY(u2gnn_segment_attn_bwd(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, c.O, dO, dp, c.stats, pd,
-                                             s->attn, q_scale, dQKV, 3 * dp, seg_delta, N, Np, st));
+            U2GNN_TRY(u2gnn_segment_attn_bwd_bias(c.QKV, 3 * dp, (int32_t)dp, D.seg, D.n_seg, D.pair_off, D.n_pairs,
+                                                  D.seg_bias, c.O, dO, dp, c.stats, pd, s->attn, q_scale, dQKV, 3 * dp,
+                                                  seg_delta, D.seg_dbias, N, Np, st));
         break;
     }
     case Attn::csr: {
@@ -964,16 +972,33 @@ int u2gnn_layer_sizes(const u2gnn_layer_dims *dims, float p_drop, int64_t *ctx_b
     return u2gnn_layer_sizes_seg(dims, p_drop, 0, ctx_bytes, fwd_ws_bytes, bwd_ws_bytes);
 }
 
-int u2gnn_layer_fwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
-                         const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, const float *bias,
-                         void *stream) {
-    if (!dims_ok(dims) || !w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias);
+// the forward of every pattern: D from make_dims (and, for segments with a bias, seg_pairs), still to be checked
+static int layer_fwd_call(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s, const float *X,
+                          float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes, void *stream) {
+    if (!w || !s || !X || !X2 || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     return plan_then_run(ctx, ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
         return layer_fwd(D, w, s, X, X2, C, W, ctx != nullptr, reinterpret_cast<hipStream_t>(stream));
     });
+}
+
+int u2gnn_layer_fwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                         const int64_t *seg_offsets, int32_t n_seg, const u2gnn_csr_attn *A, const float *bias,
+                         void *stream) {
+    if (!dims_ok(dims)) return U2GNN_E_ARG;
+    return layer_fwd_call(make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias), w, s, X, X2, ctx, ctx_bytes, ws,
+                          ws_bytes, stream);
+}
+
+int u2gnn_layer_fwd_segb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                         const int64_t *seg_offsets, int32_t n_seg, const int64_t *pair_off, int64_t n_pairs,
+                         const float *bias, void *stream) {
+    if (!dims_ok(dims)) return U2GNN_E_ARG;
+    Dims D = make_dims(dims, seg_offsets, n_seg, nullptr, 0);
+    if (bias) D.pair_off = pair_off, D.n_pairs = n_pairs, D.seg_bias = bias;   // no bias: the _seg call exactly
+    return layer_fwd_call(D, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, stream);
 }
 
 int u2gnn_layer_fwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
@@ -994,19 +1019,39 @@ int u2gnn_layer_fwd(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, c
     return u2gnn_layer_fwd_seg(dims, w, s, X, X2, ctx, ctx_bytes, ws, ws_bytes, nullptr, 0, stream);
 }
 
-int u2gnn_layer_bwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
-                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
-                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
-                         int32_t n_seg, const u2gnn_csr_attn *A, const float *bias, float *dbias, void *stream,
-                         void *side_stream) {
-    if (!dims_ok(dims) || !w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
-    const Dims D = make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias, dbias);
+// the backward of every pattern, as layer_fwd_call
+static int layer_bwd_call(const Dims &D, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s, const float *X,
+                          const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX, const u2gnn_layer_grads *g,
+                          void *ws, int64_t ws_bytes, void *stream, void *side_stream) {
+    if (!w || !s || !X || !ctx || !dX2 || !g || (!ws && ws_bytes > 0)) return U2GNN_E_ARG;
     if (!pattern_ok(D, false)) return U2GNN_E_ARG;
     // (planned with this call's schedule: its streams and whether dX is wanted)
     return plan_then_run(const_cast<void *>(ctx), ctx_bytes, ws, ws_bytes, [&](Arena &C, Arena &W) {
         return layer_bwd(D, w, s, X, C, dX2, dX, g, W, reinterpret_cast<hipStream_t>(stream),
                          reinterpret_cast<hipStream_t>(side_stream), dX != nullptr);
     });
+}
+
+int u2gnn_layer_bwd_csrb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                         int32_t n_seg, const u2gnn_csr_attn *A, const float *bias, float *dbias, void *stream,
+                         void *side_stream) {
+    if (!dims_ok(dims)) return U2GNN_E_ARG;
+    return layer_bwd_call(make_dims(dims, seg_offsets, n_seg, A, A ? A->nnz : 0, bias, dbias), w, s, X, ctx, ctx_bytes,
+                          dX2, dX, g, ws, ws_bytes, stream, side_stream);
+}
+
+int u2gnn_layer_bwd_segb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                         int32_t n_seg, const int64_t *pair_off, int64_t n_pairs, const float *bias, float *dbias,
+                         void *stream, void *side_stream) {
+    if (!dims_ok(dims)) return U2GNN_E_ARG;
+    Dims D = make_dims(dims, seg_offsets, n_seg, nullptr, 0);
+    if (bias) D.pair_off = pair_off, D.n_pairs = n_pairs, D.seg_bias = bias;   // no bias: the _seg call exactly
+    D.seg_dbias = dbias;                                                       // (without a bias: refused)
+    return layer_bwd_call(D, w, s, X, ctx, ctx_bytes, dX2, dX, g, ws, ws_bytes, stream, side_stream);
 }
 
 int u2gnn_layer_bwd_csr(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,

@@ -15,6 +15,13 @@
 // Segments: the offsets live on the device only.  Every row finds its segment by binary search, every bound is
 // clamped to [0, N], a row covered by no segment gets zero output, and a tile that straddles segments walks the
 // union of its rows' ranges and masks per row.
+//
+// BIAS (u2gnn_segment_attn_*_bias): an additive term per (query, key) pair of a segment on the score before the
+// softmax -- the model's learned scalar per shortest-path distance.  Segment g's n_g^2 pairs are the floats
+// bias[pair_off[g] ..], row-major [query][key]; the entry id of a pair is formed from the row's clamped range, and
+// an id outside [0, n_pairs) reads 0 and writes nothing, so any pair_off content is memory-safe as the offsets are.
+// The query-tile backward also stores dS per pair (dL/dbias): every pair once, no atomics.  A compile-time flag of
+// the three kernels; the instantiations without it are the kernels as they were.
 #include <mutex>
 #include <set>
 #include <utility>
@@ -34,9 +41,10 @@ constexpr size_t SEG_LDS_LIMIT = 160 * 1024;
 __host__ __device__ __forceinline__ int seg_ld(int dp) { return dp + 4; }
 
 // the key range [lo, hi) of row i: the segment g with off[g] <= i < off[g+1] (the last such g, so empty segments
-// are skipped), bounds clamped to [0, N]; lo = hi = 0 when no segment covers the row
-__device__ __forceinline__ void seg_range(const int64_t *off, int n_seg, int64_t i, int64_t N, int &lo, int &hi) {
-    lo = hi = 0;
+// are skipped), bounds clamped to [0, N]; lo = hi = 0 when no segment covers the row.  g: that segment's index
+__device__ __forceinline__ void seg_range(const int64_t *off, int n_seg, int64_t i, int64_t N, int &lo, int &hi,
+                                          int &g) {
+    lo = hi = g = 0;
     if (i >= N || off[0] > i) return;
     int a = 0, b = n_seg;   // off[a] <= i; the answer is in [a, b)
     while (b - a > 1) {
@@ -46,17 +54,33 @@ __device__ __forceinline__ void seg_range(const int64_t *off, int n_seg, int64_t
     }
     const int64_t s = min(max(off[a], (int64_t)0), N), e = min(max(off[a + 1], (int64_t)0), N);
     if (i < s || i >= e) return;
-    lo = (int)s, hi = (int)e;
+    lo = (int)s, hi = (int)e, g = a;
 }
 
-// the ranges of the block's T rows into rlo / rhi (LDS)
+// the ranges of the block's T rows into rlo / rhi (LDS).  BIAS: also the row's part of its pairs' entry ids into
+// rpb, so that the pair of query i and key j of a segment [lo, hi) of n rows at pair base pb is entry
+//   pb + (i - lo) n + (j - lo) = rpb[i] + j      with the block's rows as queries (COL false), or
+//                              = rpb[j] + i n    with the block's rows as keys (COL true).
+// Unsigned arithmetic: a wild pair_off wraps instead of overflowing, and seg_pair_bias refuses the id
+template <bool BIAS, bool COL>
 __device__ __forceinline__ void seg_tile_ranges(const int64_t *off, int n_seg, int64_t row0, int T, int64_t N, int *rlo,
-                                                int *rhi) {
+                                                int *rhi, const int64_t *pair_off, uint64_t *rpb) {
     if ((int)threadIdx.x < T) {
-        int lo, hi;
-        seg_range(off, n_seg, row0 + threadIdx.x, N, lo, hi);
+        int lo, hi, g;
+        seg_range(off, n_seg, row0 + threadIdx.x, N, lo, hi, g);
         rlo[threadIdx.x] = lo, rhi[threadIdx.x] = hi;
+        if constexpr (BIAS) {
+            const uint64_t r = (uint64_t)(row0 + threadIdx.x) - (uint64_t)lo, n = (uint64_t)(hi - lo);
+            uint64_t b = 0;
+            if (hi > lo) b = (uint64_t)pair_off[g] + (COL ? r - (uint64_t)lo * n : r * n - (uint64_t)lo);
+            rpb[threadIdx.x] = b;
+        }
     }
+}
+
+// the bias of entry e, 0 for an id outside [0, n_pairs)
+__device__ __forceinline__ float seg_pair_bias(const float *bias, uint64_t e, int64_t n_pairs) {
+    return e < (uint64_t)n_pairs ? bias[e] : 0.f;
 }
 
 // the union of the rows' ranges (after a barrier): [beg, end), empty when no row is covered
@@ -184,18 +208,20 @@ __device__ __forceinline__ float seg_row_max(float v, int tpr) {
 // Forward.  Block = TQ query rows; per key tile: K -> scores -> (V staged over K beside) the online softmax and
 // dropout -> O accumulators rescaled and advanced.  The accumulators' owner thread holds a float4 column group of
 // RB rows (dq * TQ / RB <= 256 threads).
-template <int RB>
+template <int RB, bool BIAS>
 __global__ void __launch_bounds__(SEG_THREADS)
     segment_attn_fwd_kernel(const float *QKV, int64_t ldq, int dp, const int64_t *off, int n_seg, float *O, int64_t ldo,
                             float *stats, float p, uint64_t seed, const uint64_t *seed_epoch, int64_t N,
-                            int64_t rows_pad, int TQ, int TK) {
+                            int64_t rows_pad, int TQ, int TK, const float *bias, const int64_t *pair_off,
+                            int64_t n_pairs) {
     seed = u2gnn_seed(seed, seed_epoch);
     extern __shared__ __align__(16) float seg_sm[];
     const int LD = seg_ld(dp), dq = dp / 4, ldc = TK + 1, tid = threadIdx.x;
     float *Qs = seg_sm, *KV = Qs + TQ * LD, *S = KV + TK * LD, *alpha = S + TQ * ldc;
     int *rlo = reinterpret_cast<int *>(alpha + TQ), *rhi = rlo + TQ;
+    uint64_t *rpb = reinterpret_cast<uint64_t *>(rhi + TQ);   // BIAS only (seg_lds)
     const int64_t row0 = (int64_t)blockIdx.x * TQ;
-    seg_tile_ranges(off, n_seg, row0, TQ, N, rlo, rhi);
+    seg_tile_ranges<BIAS, false>(off, n_seg, row0, TQ, N, rlo, rhi, pair_off, rpb);
     seg_stage(QKV, ldq, row0, N, 0, TQ, dp, Qs);
     __syncthreads();
     int kbeg, kend;
@@ -203,6 +229,8 @@ __global__ void __launch_bounds__(SEG_THREADS)
     // softmax role: tpr consecutive lanes per row, each holding the row's running (max, sum)
     const int tpr = SEG_THREADS / TQ, si = tid / tpr, sub = tid - si * tpr;
     const int my_lo = rlo[si], my_hi = rhi[si];
+    uint64_t my_pb = 0;   // the row's pairs: entry my_pb + key (the lanes of a row read consecutive floats)
+    if constexpr (BIAS) my_pb = rpb[si];
     const uint32_t rkey = u2gnn_row_key(seed, (uint32_t)(row0 + si)), thr = u2gnn_keep_thr(p);
     const float ks = p > 0.f ? 1.f / (1.f - p) : 1.f;
     float m_run = -INFINITY, l_run = 0.f;
@@ -226,7 +254,15 @@ __global__ void __launch_bounds__(SEG_THREADS)
         float tmax = -INFINITY;
         for (int j = sub; j < TK; j += tpr) {
             const int kj = k0 + j;
-            if (kj >= my_lo && kj < my_hi) tmax = fmaxf(tmax, srow[j]);
+            if constexpr (BIAS) {   // the biased score replaces the product: the second sweep reads it back
+                if (kj >= my_lo && kj < my_hi) {
+                    const float s = srow[j] + seg_pair_bias(bias, my_pb + (uint64_t)kj, n_pairs);
+                    srow[j] = s;
+                    tmax = fmaxf(tmax, s);
+                }
+            } else {
+                if (kj >= my_lo && kj < my_hi) tmax = fmaxf(tmax, srow[j]);
+            }
         }
         tmax = seg_row_max(tmax, tpr);
         const float m_new = fmaxf(m_run, tmax);
@@ -276,12 +312,13 @@ __global__ void __launch_bounds__(SEG_THREADS)
 // Backward over query tiles: delta_i = rowsum(dO_i * O_i) (kept in delta_ws for the key-tile launch), then per key
 // tile S = Qs K^T and dPd = dO V^T, dS = P o (keep dPd / (1-p) - delta) with P recomputed from the saved row
 // statistics, dQ += dS K.  dQKV[:, 0:dp] = q_scale * dQ.
-template <int RB>
+template <int RB, bool BIAS>
 __global__ void __launch_bounds__(SEG_THREADS)
     segment_attn_bwd_q_kernel(const float *QKV, int64_t ldq, int dp, const int64_t *off, int n_seg, const float *O,
                               const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed,
                               const uint64_t *seed_epoch, float q_scale, float *dQKV, int64_t ldg, float *delta_ws,
-                              int64_t N, int64_t rows_pad, int TQ, int TK) {
+                              int64_t N, int64_t rows_pad, int TQ, int TK, const float *bias, const int64_t *pair_off,
+                              int64_t n_pairs, float *dbias) {
     seed = u2gnn_seed(seed, seed_epoch);
     extern __shared__ __align__(16) float seg_sm[];
     const int LD = seg_ld(dp), dq = dp / 4, ldc = TK + 1, tid = threadIdx.x;
@@ -289,8 +326,9 @@ __global__ void __launch_bounds__(SEG_THREADS)
     float *S = Vs + TK * LD, *dP = S + TQ * ldc;
     float *rm = dP + TQ * ldc, *rinv = rm + TQ, *rdel = rinv + TQ;
     int *rlo = reinterpret_cast<int *>(rdel + TQ), *rhi = rlo + TQ;
+    uint64_t *rpb = reinterpret_cast<uint64_t *>(rhi + TQ);   // BIAS only (seg_lds)
     const int64_t row0 = (int64_t)blockIdx.x * TQ;
-    seg_tile_ranges(off, n_seg, row0, TQ, N, rlo, rhi);
+    seg_tile_ranges<BIAS, false>(off, n_seg, row0, TQ, N, rlo, rhi, pair_off, rpb);
     seg_stage(QKV, ldq, row0, N, 0, TQ, dp, Qs);
     seg_stage(dO, ldo, row0, N, 0, TQ, dp, dOs);
     {   // delta and the saved statistics of the tile's rows (zeros for rows >= N)
@@ -341,9 +379,18 @@ __global__ void __launch_bounds__(SEG_THREADS)
             const int i = e >> tk_sh, j = e & (TK - 1), kj = k0 + j;
             float ds = 0.f;
             if (kj >= rlo[i] && kj < rhi[i]) {
-                const float pv = expf(S[i * ldc + j] - rm[i]) * rinv[i];
+                float s = S[i * ldc + j];
+                uint64_t pe = 0;
+                if constexpr (BIAS) {
+                    pe = rpb[i] + (uint64_t)kj;
+                    s += seg_pair_bias(bias, pe, n_pairs);
+                }
+                const float pv = expf(s - rm[i]) * rinv[i];
                 const bool keep = p > 0.f ? u2gnn_keep(seed, (uint32_t)(row0 + i), (uint32_t)kj, p) : true;
                 ds = pv * ((keep ? dP[i * ldc + j] * ks : 0.f) - rdel[i]);
+                if constexpr (BIAS) {   // dL/dbias of the pair: each (i, kj) is formed here exactly once
+                    if (dbias && pe < (uint64_t)n_pairs) dbias[pe] = ds;
+                }
             }
             S[i * ldc + j] = ds;
         }
@@ -365,12 +412,12 @@ __global__ void __launch_bounds__(SEG_THREADS)
 // Backward over key tiles: the block owns TQ key rows (K, V images) and walks the query tiles of their segments
 // (Q, dO images, the queries' statistics and delta): S^T = K Qs^T, dPd^T = V dO^T, then dK += dS^T Qs and
 // dV += Pd^T dO.  dQKV[:, dp:3dp] = [dK | dV].
-template <int RB>
+template <int RB, bool BIAS>
 __global__ void __launch_bounds__(SEG_THREADS)
     segment_attn_bwd_kv_kernel(const float *QKV, int64_t ldq, int dp, const int64_t *off, int n_seg, const float *dO,
                                int64_t ldo, const float *stats, float p, uint64_t seed, const uint64_t *seed_epoch,
                                float *dQKV, int64_t ldg, const float *delta_ws, int64_t N, int64_t rows_pad, int TQ,
-                               int TK) {
+                               int TK, const float *bias, const int64_t *pair_off, int64_t n_pairs) {
     seed = u2gnn_seed(seed, seed_epoch);
     extern __shared__ __align__(16) float seg_sm[];
     const int LD = seg_ld(dp), dq = dp / 4, ldc = TK + 1, tid = threadIdx.x;
@@ -378,8 +425,9 @@ __global__ void __launch_bounds__(SEG_THREADS)
     float *C1 = dOs + TK * LD, *C2 = C1 + TQ * ldc;   // dS^T, Pd^T: [own key][query]
     float *om = C2 + TQ * ldc, *oinv = om + TK, *odel = oinv + TK;
     int *rlo = reinterpret_cast<int *>(odel + TK), *rhi = rlo + TQ;
+    uint64_t *rpb = reinterpret_cast<uint64_t *>(rhi + TQ);   // BIAS only (seg_lds)
     const int64_t row0 = (int64_t)blockIdx.x * TQ;
-    seg_tile_ranges(off, n_seg, row0, TQ, N, rlo, rhi);
+    seg_tile_ranges<BIAS, true>(off, n_seg, row0, TQ, N, rlo, rhi, pair_off, rpb);
     seg_stage(QKV, ldq, row0, N, dp, TQ, dp, Ks);
     seg_stage(QKV, ldq, row0, N, 2 * dp, TQ, dp, Vs);
     __syncthreads();
@@ -419,7 +467,10 @@ __global__ void __launch_bounds__(SEG_THREADS)
             const int j = e >> tk_sh, t = e & (TK - 1), qi = q0 + t;   // own key row j, query column t
             float ds = 0.f, pd = 0.f;
             if (qi >= rlo[j] && qi < rhi[j]) {
-                const float pv = expf(C1[j * ldc + t] - om[t]) * oinv[t];
+                float s = C1[j * ldc + t];
+                if constexpr (BIAS)   // down a column of the segment's block: the lanes' queries are n floats apart
+                    s += seg_pair_bias(bias, rpb[j] + (uint64_t)qi * (uint64_t)(rhi[j] - rlo[j]), n_pairs);
+                const float pv = expf(s - om[t]) * oinv[t];
                 const bool keep = p > 0.f ? u2gnn_keep(seed, (uint32_t)qi, (uint32_t)(row0 + j), p) : true;
                 pd = keep ? pv * ks : 0.f;
                 ds = pv * ((keep ? C2[j * ldc + t] * ks : 0.f) - odel[t]);
@@ -454,13 +505,15 @@ struct SegTiles {
     int tq, tk, rb;
     size_t lds;
 };
-size_t seg_lds(int dp, int tq, int tk, bool bwd) {
+// BIAS adds the rows' entry bases (one uint64 per own row) and moves no tile choice: the tiles are chosen as without
+// it, so a zero bias walks the same tiles in the same order and gives the plain kernels' bits
+size_t seg_lds(int dp, int tq, int tk, bool bwd, bool bias = false) {
     const size_t LD = (size_t)seg_ld(dp);
     const size_t fl = bwd ? 2 * (size_t)(tq + tk) * LD + 2 * (size_t)tq * (tk + 1) + 3 * (size_t)std::max(tq, tk) + 2 * tq
                           : (size_t)(tq + tk) * LD + (size_t)tq * (tk + 1) + 3 * (size_t)tq;
-    return fl * sizeof(float);
+    return (fl + (bias ? 2 * (size_t)tq : 0)) * sizeof(float);
 }
-SegTiles seg_tiles(int dp, bool bwd) {
+SegTiles seg_tiles(int dp, bool bwd, bool bias = false) {
     SegTiles t;
     t.tq = dp > 512 ? 8 : 16;
     t.tk = 64;
@@ -469,7 +522,7 @@ SegTiles seg_tiles(int dp, bool bwd) {
     if (t.tk == 64 && seg_lds(dp, t.tq, 64, bwd) > SEG_LDS_LIMIT / 2 && seg_lds(dp, t.tq, 32, bwd) <= SEG_LDS_LIMIT / 2)
         t.tk = 32;
     while (t.tk > 8 && t.tk * (dp / 4) > SEG_PF * SEG_THREADS) t.tk >>= 1;   // a walked tile fits the prefetch registers
-    t.lds = seg_lds(dp, t.tq, t.tk, bwd);
+    t.lds = seg_lds(dp, t.tq, t.tk, bwd, bias);
     // accumulator rows per thread: dq column groups x tq / rb row blocks within the block's 256 threads
     const int per = std::max(1, SEG_THREADS / (dp / 4));
     t.rb = 1;
@@ -500,44 +553,100 @@ int seg_check(const void *a, const void *b, const void *c, const void *d, int32_
     return U2GNN_OK;
 }
 
+// a bias needs its pair offsets and at least one pair, its gradient needs the bias
+bool seg_bias_ok(const float *bias, const int64_t *pair_off, int64_t n_pairs, const float *dbias) {
+    if (!bias) return dbias == nullptr;
+    return pair_off && n_pairs >= 1;
+}
+
 #define U2GNN_TRY_SEG(x)                 \
     do {                                 \
         const int rc_ = (x);             \
         if (rc_ != U2GNN_OK) return rc_; \
     } while (0)
 
-// one instantiation per accumulator row count
-#define SEG_DISPATCH(rb, LAUNCH)    \
-    switch (rb) {                   \
-        case 1: LAUNCH(1); break;   \
-        case 2: LAUNCH(2); break;   \
-        case 4: LAUNCH(4); break;   \
-        case 8: LAUNCH(8); break;   \
+// one instantiation per accumulator row count, with and without the bias
+#define SEG_DISPATCH_RB(rb, LAUNCH, B) \
+    switch (rb) {                      \
+        case 1: LAUNCH(1, B); break;   \
+        case 2: LAUNCH(2, B); break;   \
+        case 4: LAUNCH(4, B); break;   \
+        case 8: LAUNCH(8, B); break;   \
         default: return U2GNN_E_SHAPE; \
+    }
+#define SEG_DISPATCH(rb, with_bias, LAUNCH)       \
+    if (with_bias) {                              \
+        SEG_DISPATCH_RB(rb, LAUNCH, true)         \
+    } else {                                      \
+        SEG_DISPATCH_RB(rb, LAUNCH, false)        \
     }
 
 }  // namespace
 
 extern "C" {
 
+int u2gnn_segment_attn_fwd_bias(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                                const int64_t *pair_off, int64_t n_pairs, const float *bias, float *O, int64_t ldo,
+                                float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad, void *stream) {
+    U2GNN_TRY_SEG(seg_check(QKV, seg_offsets, O, stats, dp, n_seg, p, N, rows_pad));
+    if (!seg_bias_ok(bias, pair_off, n_pairs, nullptr)) return U2GNN_E_ARG;
+    if ((ldq & 3) || (ldo & 3) || ldq < 3 * (int64_t)dp || ldo < dp) return U2GNN_E_ARG;
+    if (((uintptr_t)QKV & 15) || ((uintptr_t)O & 15) || ((uintptr_t)stats & 7)) return U2GNN_E_ALIGN;
+    if (bias && (((uintptr_t)bias & 3) || ((uintptr_t)pair_off & 7))) return U2GNN_E_ALIGN;
+    const SegTiles t = seg_tiles(dp, false, bias != nullptr);
+    if (t.lds > SEG_LDS_LIMIT) return U2GNN_E_SHAPE;
+    const unsigned grid = (unsigned)((rows_pad + t.tq - 1) / t.tq);
+#define SEG_FWD(R, B)                                                                                               \
+    do {                                                                                                            \
+        auto kern = segment_attn_fwd_kernel<R, B>;                                                                  \
+        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kern)));                                         \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,      \
+                           seg_offsets, (int)n_seg, O, ldo, stats, p, seed, u2gnn_cur_epoch(), N, rows_pad, t.tq, t.tk, \
+                           bias, pair_off, n_pairs);                                                                \
+    } while (0)
+    SEG_DISPATCH(t.rb, bias != nullptr, SEG_FWD)
+#undef SEG_FWD
+    return u2gnn_launch_status();
+}
+
 int u2gnn_segment_attn_fwd(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
                            float *O, int64_t ldo, float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad,
                            void *stream) {
+    return u2gnn_segment_attn_fwd_bias(QKV, ldq, dp, seg_offsets, n_seg, nullptr, 0, nullptr, O, ldo, stats, p, seed, N,
+                                       rows_pad, stream);
+}
+
+int u2gnn_segment_attn_bwd_bias(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                                const int64_t *pair_off, int64_t n_pairs, const float *bias, const float *O,
+                                const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed, float q_scale,
+                                float *dQKV, int64_t ldg, float *delta_ws, float *dbias, int64_t N, int64_t rows_pad,
+                                void *stream) {
     U2GNN_TRY_SEG(seg_check(QKV, seg_offsets, O, stats, dp, n_seg, p, N, rows_pad));
-    if ((ldq & 3) || (ldo & 3) || ldq < 3 * (int64_t)dp || ldo < dp) return U2GNN_E_ARG;
-    if (((uintptr_t)QKV & 15) || ((uintptr_t)O & 15) || ((uintptr_t)stats & 7)) return U2GNN_E_ALIGN;
-    const SegTiles t = seg_tiles(dp, false);
+    if (!dO || !dQKV || !delta_ws || !seg_bias_ok(bias, pair_off, n_pairs, dbias)) return U2GNN_E_ARG;
+    if ((ldq & 3) || (ldo & 3) || (ldg & 3) || ldq < 3 * (int64_t)dp || ldo < dp || ldg < 3 * (int64_t)dp)
+        return U2GNN_E_ARG;
+    if (((uintptr_t)QKV & 15) || ((uintptr_t)O & 15) || ((uintptr_t)dO & 15) || ((uintptr_t)dQKV & 15))
+        return U2GNN_E_ALIGN;
+    if (bias && (((uintptr_t)bias & 3) || ((uintptr_t)dbias & 3) || ((uintptr_t)pair_off & 7))) return U2GNN_E_ALIGN;
+    const SegTiles t = seg_tiles(dp, true, bias != nullptr);
     if (t.lds > SEG_LDS_LIMIT) return U2GNN_E_SHAPE;
     const unsigned grid = (unsigned)((rows_pad + t.tq - 1) / t.tq);
-#define SEG_FWD(R)                                                                                                  \
-    do {                                                                                                            \
-        auto kern = segment_attn_fwd_kernel<R>;                                                                     \
-        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kern)));                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,      \
-                           seg_offsets, (int)n_seg, O, ldo, stats, p, seed, u2gnn_cur_epoch(), N, rows_pad, t.tq, t.tk); \
+#define SEG_BWD(R, B)                                                                                                \
+    do {                                                                                                             \
+        auto kq = segment_attn_bwd_q_kernel<R, B>;                                                                   \
+        auto kkv = segment_attn_bwd_kv_kernel<R, B>;                                                                 \
+        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kq)));                                            \
+        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kkv)));                                           \
+        hipLaunchKernelGGL(kq, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,         \
+                           seg_offsets, (int)n_seg, O, dO, ldo, stats, p, seed, u2gnn_cur_epoch(), q_scale, dQKV, ldg, \
+                           delta_ws, N, rows_pad, t.tq, t.tk, bias, pair_off, n_pairs, dbias);                       \
+        U2GNN_TRY_SEG(u2gnn_launch_status());                                                                        \
+        hipLaunchKernelGGL(kkv, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,        \
+                           seg_offsets, (int)n_seg, dO, ldo, stats, p, seed, u2gnn_cur_epoch(), dQKV, ldg,           \
+                           (const float *)delta_ws, N, rows_pad, t.tq, t.tk, bias, pair_off, n_pairs);               \
     } while (0)
-    SEG_DISPATCH(t.rb, SEG_FWD)
-#undef SEG_FWD
+    SEG_DISPATCH(t.rb, bias != nullptr, SEG_BWD)
+#undef SEG_BWD
     return u2gnn_launch_status();
 }
 
@@ -545,32 +654,8 @@ int u2gnn_segment_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const int6
                            const float *O, const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed,
                            float q_scale, float *dQKV, int64_t ldg, float *delta_ws, int64_t N, int64_t rows_pad,
                            void *stream) {
-    U2GNN_TRY_SEG(seg_check(QKV, seg_offsets, O, stats, dp, n_seg, p, N, rows_pad));
-    if (!dO || !dQKV || !delta_ws) return U2GNN_E_ARG;
-    if ((ldq & 3) || (ldo & 3) || (ldg & 3) || ldq < 3 * (int64_t)dp || ldo < dp || ldg < 3 * (int64_t)dp)
-        return U2GNN_E_ARG;
-    if (((uintptr_t)QKV & 15) || ((uintptr_t)O & 15) || ((uintptr_t)dO & 15) || ((uintptr_t)dQKV & 15))
-        return U2GNN_E_ALIGN;
-    const SegTiles t = seg_tiles(dp, true);
-    if (t.lds > SEG_LDS_LIMIT) return U2GNN_E_SHAPE;
-    const unsigned grid = (unsigned)((rows_pad + t.tq - 1) / t.tq);
-#define SEG_BWD(R)                                                                                                   \
-    do {                                                                                                             \
-        auto kq = segment_attn_bwd_q_kernel<R>;                                                                      \
-        auto kkv = segment_attn_bwd_kv_kernel<R>;                                                                    \
-        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kq)));                                            \
-        U2GNN_TRY_SEG(seg_lds_optin(reinterpret_cast<const void *>(kkv)));                                           \
-        hipLaunchKernelGGL(kq, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,         \
-                           seg_offsets, (int)n_seg, O, dO, ldo, stats, p, seed, u2gnn_cur_epoch(), q_scale, dQKV, ldg, \
-                           delta_ws, N, rows_pad, t.tq, t.tk);                                                       \
-        U2GNN_TRY_SEG(u2gnn_launch_status());                                                                        \
-        hipLaunchKernelGGL(kkv, dim3(grid), dim3(SEG_THREADS), t.lds, u2gnn_stream(stream), QKV, ldq, (int)dp,        \
-                           seg_offsets, (int)n_seg, dO, ldo, stats, p, seed, u2gnn_cur_epoch(), dQKV, ldg,           \
-                           (const float *)delta_ws, N, rows_pad, t.tq, t.tk);                                        \
-    } while (0)
-    SEG_DISPATCH(t.rb, SEG_BWD)
-#undef SEG_BWD
-    return u2gnn_launch_status();
+    return u2gnn_segment_attn_bwd_bias(QKV, ldq, dp, seg_offsets, n_seg, nullptr, 0, nullptr, O, dO, ldo, stats, p, seed,
+                                       q_scale, dQKV, ldg, delta_ws, nullptr, N, rows_pad, stream);
 }
 
 }  // extern "C"

@@ -28,13 +28,19 @@ independent of the batch; reference-style tensor inputs carry no edges, so ``for
 (``Adjacency.from_csr(rowptr, colidx, N, device, etype=etype)`` of ``store.adjacency(graph_ids, hops=H)``) and each
 encoder layer adds a learned scalar per shortest-path distance to its scores: ONE more parameter, ``hop_bias``
 [L, T, H + 1], zero-initialised and registered after every other, so the rest of the model keeps its values under a
-seed and, without ``hops``, the state_dict keys are the reference's.
+seed and, without ``hops``, the state_dict keys are the reference's;
+``distances`` = None, or H in [1, 31] with attention="graphs" (and without ``hops``): every node still attends over ALL
+nodes of its graph, and each encoder layer adds hop_bias[l][t][min(shortest-path distance, H)] to the score of a pair
+(index H also for a pair no path joins) -- Graphormer's spatial encoding on the per-graph kernels.  The same ONE more
+parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last); the batch carries the pair types as
+``DeviceBatch.pairs`` = ``PairTypes.from_store(store, graph_ids, N, device, H)``.
 """
 import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from u2gnn_hip.core import DeviceBatch, FlatParams, SupCore, check_attention, check_hops, hop_bias_last
+from u2gnn_hip.core import (DeviceBatch, FlatParams, SupCore, check_attention, check_distances, check_hops,
+                            hop_bias_last)
 
 
 class _SupFunction(torch.autograd.Function):
@@ -56,7 +62,8 @@ class _SupFunction(torch.autograd.Function):
 class TransformerU2GNN(nn.Module):
 
     def __init__(self, feature_dim_size, ff_hidden_size, num_classes,
-                 num_self_att_layers, dropout, num_U2GNN_layers, precision="fp32", attention="nodes", hops=None):
+                 num_self_att_layers, dropout, num_U2GNN_layers, precision="fp32", attention="nodes", hops=None,
+                 distances=None):
         super(TransformerU2GNN, self).__init__()
         self.feature_dim_size = feature_dim_size
         self.ff_hidden_size = ff_hidden_size
@@ -67,6 +74,7 @@ class TransformerU2GNN(nn.Module):
         self.precision = precision
         self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
+        self.distances = check_distances(distances, attention, hops)
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()
         for _ in range(self.num_U2GNN_layers):
@@ -79,8 +87,9 @@ class TransformerU2GNN(nn.Module):
         for _ in range(self.num_U2GNN_layers):
             self.predictions.append(nn.Linear(self.feature_dim_size, self.num_classes))
             self.dropouts.append(nn.Dropout(dropout))
-        if self.hops:   # after every reference parameter; zeros: torch's generator is not touched
-            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers, self.hops + 1))
+        if self.hops or self.distances:   # after every reference parameter; zeros: torch's generator is not touched
+            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers,
+                                                     (self.hops or self.distances) + 1))
         self._core = None
 
     def named_parameters(self, prefix='', recurse=True, remove_duplicate=True):

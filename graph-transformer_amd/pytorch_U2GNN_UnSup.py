@@ -21,7 +21,10 @@ be a ``DeviceBatch`` whose graphs are consecutive row ranges, as ``from_offsets`
 ``graphs = DeviceGraphs.from_store(store, device, hops)``, what ``DeviceBatch.from_store(hb, X_dev, graphs=graphs)``
 sets; else a ValueError).  ``hops`` = None, or H in [1, 31]
 with attention="edges": attention over the H-hop neighbourhood with a learned bias per shortest-path distance, one more
-trainable parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last), as in pytorch_U2GNN_Sup.
+trainable parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last), as in pytorch_U2GNN_Sup.  ``distances`` = None,
+or H in [1, 31] with attention="graphs" (not with ``hops``): attention over the whole graph with hop_bias[l][t][min(
+shortest-path distance, H)] on every pair's score (H also for unconnected pairs); the batch's ``pairs`` is
+``PairTypes.from_store(store, graph_ids, N, device, H)``, as in pytorch_U2GNN_Sup.
 """
 import math
 
@@ -31,7 +34,7 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from sampled_softmax import SampledSoftmax
 from u2gnn_hip import kernels as K
-from u2gnn_hip.core import DeviceBatch, check_attention, check_hops, hop_bias_last
+from u2gnn_hip.core import DeviceBatch, check_attention, check_distances, check_hops, hop_bias_last
 from u2gnn_hip.engine import site_seed
 from u2gnn_hip.unsup import SITE_SS_DROP, UnSupCore
 
@@ -73,7 +76,7 @@ class TransformerU2GNN(nn.Module):
     def __init__(self, vocab_size, feature_dim_size, ff_hidden_size, sampled_num,
                  num_self_att_layers, num_U2GNN_layers, dropout, device, sampler_type='default',
                  loss_type='default', adj_mat=None, single_layer_only=True, precision="fp32", attention="nodes",
-                 hops=None):
+                 hops=None, distances=None):
         super(TransformerU2GNN, self).__init__()
         if sampler_type != 'default' or loss_type != 'default':
             raise NotImplementedError("only sampler_type='default', loss_type='default' (graph-level U2GNN) "
@@ -81,6 +84,7 @@ class TransformerU2GNN(nn.Module):
         self.feature_dim_size = feature_dim_size
         self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
+        self.distances = check_distances(distances, attention, hops)
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size
         self.num_self_att_layers = num_self_att_layers
@@ -104,8 +108,9 @@ class TransformerU2GNN(nn.Module):
         self.ss = SampledSoftmax(self.vocab_size, self.sampled_num, self.feature_dim_size * self.num_U2GNN_layers,
                                  self.device)
         self.reset_parameters()
-        if self.hops:   # after every other parameter; zeros: torch's generator is not touched
-            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers, self.hops + 1))
+        if self.hops or self.distances:   # after every other parameter; zeros: torch's generator is not touched
+            self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers,
+                                                     (self.hops or self.distances) + 1))
         self._core = None
 
     def reset_parameters(self):
@@ -123,7 +128,7 @@ class TransformerU2GNN(nn.Module):
         return self._core
 
     def trainable_names(self):
-        """Parameters on the loss path (encoders + ss.weight, and hop_bias with ``hops``)."""
+        """Parameters on the loss path (encoders + ss.weight, and hop_bias with ``hops`` or ``distances``)."""
         return [n for n, _ in self.named_parameters()
                 if n.startswith("u2gnn_layers.") or n in ("ss.weight", "hop_bias")]
 

@@ -10,7 +10,7 @@ Execution: the default trainer is the fused HIP step (u2gnn_hip.train.SupTrainer
 backward into a flat grad buffer, device-side clip + Adam, no per-step host sync except the loss
 readout the reference also does).  ``--autograd`` runs the reference's exact loop instead
 (model(), cross_entropy, loss.backward(), clip_grad_norm_, torch Adam, StepLR) — on the same kernels.
-Extra flags: --precision, --attention, --hops, --autograd, --max_steps (0 = full epochs), --world_size /
+Extra flags: --precision, --attention, --hops, --distances, --autograd, --max_steps (0 = full epochs), --world_size /
 --dist_backend (data parallelism, u2gnn_hip.cli: one process per GPU, a global step = world_size
 consecutive batches of the single stream with the averaged gradient, RCCL all-reduce under the backward).
 """
@@ -59,6 +59,11 @@ parser.add_argument("--hops", default=0, type=int,
                     help="with --attention edges: each node attends over every node of its graph within this many "
                          "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
                          "scores (one more parameter, hop_bias); 0 = off, the plain adjacency")
+parser.add_argument("--distances", default=0, type=int,
+                    help="with --attention graphs: every encoder layer adds a learned bias per shortest-path distance "
+                         "(clipped at this many bonds, 1..31; unconnected pairs take the last entry) to the scores of "
+                         "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
+                         "--adjacency has no effect on it")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
                     help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
                          "from a per-dataset structure kept there (built once at start; a dataset whose structure "
@@ -77,6 +82,12 @@ if args.hops and args.attention != "edges":
     parser.error("--hops needs --attention edges")
 if not 0 <= args.hops <= 31:
     parser.error("--hops must be in 0..31")
+if args.distances and args.attention != "graphs":
+    parser.error("--distances needs --attention graphs")
+if args.distances and args.hops:
+    parser.error("--distances and --hops exclude each other")
+if not 0 <= args.distances <= 31:
+    parser.error("--distances must be in 0..31")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -84,7 +95,7 @@ if _rc is not None:
 
 from pytorch_U2GNN_Sup import TransformerU2GNN, label_smoothing  # noqa: E402
 from u2gnn_hip.batching import BatchLoader, GraphStore  # noqa: E402
-from u2gnn_hip.core import Adjacency, DeviceBatch  # noqa: E402
+from u2gnn_hip.core import Adjacency, DeviceBatch, PairTypes  # noqa: E402
 from u2gnn_hip.dp import GradAllReduce, OverlappedGradAllReduce, broadcast_params  # noqa: E402
 from u2gnn_hip.train import SupTrainer  # noqa: E402
 from util import load_data, separate_data  # noqa: E402
@@ -117,7 +128,8 @@ log("Loading data... finished!")
 model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.ff_hidden_size,
                          num_classes=num_classes, dropout=args.dropout, num_self_att_layers=args.num_timesteps,
                          num_U2GNN_layers=args.num_hidden_layers, precision=args.precision,
-                         attention=args.attention, hops=args.hops or None).to(device)
+                         attention=args.attention, hops=args.hops or None,
+                         distances=args.distances or None).to(device)
 num_batches_per_epoch = int((len(train_graphs) - 1) / args.batch_size) + 1
 # global steps per epoch: each consumes world_size batches of the stream
 steps_per_epoch = -(-num_batches_per_epoch // run.world)
@@ -140,6 +152,8 @@ def to_device(hb, store=train_store):
             b.adj = dg.adjacency(hb.graph_ids, b.rowptr)
     if edges and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists), from the store
         b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
+    if args.distances:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
+        b.pairs = PairTypes.from_store(store, hb.graph_ids, b.N, device, args.distances)
     return b
 
 

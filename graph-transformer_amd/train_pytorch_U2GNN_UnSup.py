@@ -9,7 +9,7 @@ LogisticRegression(liblinear, tol=1e-3) (:164-188), stdout line (:207) and acc f
 (<run_folder>/../runs_pytorch_U2GNN_UnSup/<model_name>/checkpoints/model_acc.txt).
 
 The fork's file cannot run as shipped; this runs its working semantics
-(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --hops, --max_steps,
+(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --hops, --distances, --max_steps,
 --world_size / --dist_backend (data parallelism, u2gnn_hip.cli: rank r trains batch r of each global step
 with the r-th sample draw of the step; encoder gradients all-reduced, the touched ss.weight rows
 all-gathered, dp.UnSupGradSync).
@@ -60,6 +60,11 @@ parser.add_argument("--hops", default=0, type=int,
                          "bonds (1..31) and every encoder layer adds a learned bias per shortest-path distance to its "
                          "scores (one more parameter, hop_bias); 0 = off, the plain adjacency.  Not with --world_size "
                          "> 1: the unsupervised gradient exchange does not carry hop_bias yet")
+parser.add_argument("--distances", default=0, type=int,
+                    help="with --attention graphs: every encoder layer adds a learned bias per shortest-path distance "
+                         "(clipped at this many bonds, 1..31; unconnected pairs take the last entry) to the scores of "
+                         "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
+                         "--adjacency has no effect on it.  Not with --world_size > 1, as --hops")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
                     help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
                          "from a per-dataset structure kept there (built once at start; a dataset whose structure "
@@ -78,6 +83,14 @@ if not 0 <= args.hops <= 31:
     parser.error("--hops must be in 0..31")
 if args.hops and (args.world_size > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
     parser.error("--hops is not available with --world_size > 1 in the unsupervised trainer")
+if args.distances and args.attention != "graphs":
+    parser.error("--distances needs --attention graphs")
+if args.distances and args.hops:
+    parser.error("--distances and --hops exclude each other")
+if not 0 <= args.distances <= 31:
+    parser.error("--distances must be in 0..31")
+if args.distances and (args.world_size > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+    parser.error("--distances is not available with --world_size > 1 in the unsupervised trainer")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -85,7 +98,7 @@ if _rc is not None:
 
 from pytorch_U2GNN_UnSup import TransformerU2GNN  # noqa: E402
 from u2gnn_hip.batching import BatchLoader, GraphStore  # noqa: E402
-from u2gnn_hip.core import Adjacency, DeviceBatch  # noqa: E402
+from u2gnn_hip.core import Adjacency, DeviceBatch, PairTypes  # noqa: E402
 from u2gnn_hip.dp import UnSupGradSync, broadcast_params, max_batch_nodes  # noqa: E402
 from u2gnn_hip.unsup import UnSupTrainer, fold_accuracies, graph_embeddings  # noqa: E402
 from util import load_data, separate_data_idx  # noqa: E402
@@ -123,7 +136,8 @@ model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.
                          dropout=args.dropout, num_self_att_layers=args.num_timesteps,
                          vocab_size=vocab_size, sampled_num=args.sampled_num,
                          num_U2GNN_layers=args.num_hidden_layers, device=device, precision=args.precision,
-                         attention=args.attention, hops=args.hops or None).to(device)
+                         attention=args.attention, hops=args.hops or None,
+                         distances=args.distances or None).to(device)
 trainer = UnSupTrainer(model, lr=args.learning_rate, max_norm=0.5)
 if run.world > 1:
     broadcast_params(trainer.flat)
@@ -149,6 +163,8 @@ def train():
         b = DeviceBatch.from_store(hb, store_X, device=device, graphs=store_graphs)
         if args.attention == "edges" and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
             b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
+        if args.distances:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
+            b.pairs = PairTypes.from_store(store, hb.graph_ids, b.N, device, args.distances)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]
         sid = torch.from_numpy(draws[run.rank]).to(device)

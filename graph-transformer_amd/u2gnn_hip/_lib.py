@@ -184,6 +184,14 @@ _HIP_SIGS = {
     "u2gnn_segment_attn_fwd": ([VP, I64, I32, VP, I32, VP, I64, VP, F32, c_uint64, I64, I64, VP], c_int32),
     "u2gnn_segment_attn_bwd": ([VP, I64, I32, VP, I32, VP, VP, I64, VP, F32, c_uint64, F32, VP, I64, VP, I64, I64, VP],
                                c_int32),
+    "u2gnn_segment_attn_fwd_bias": ([VP, I64, I32, VP, I32, VP, I64, VP, VP, I64, VP, F32, c_uint64, I64, I64, VP],
+                                    c_int32),
+    "u2gnn_segment_attn_bwd_bias": ([VP, I64, I32, VP, I32, VP, I64, VP, VP, VP, I64, VP, F32, c_uint64, F32, VP, I64,
+                                     VP, VP, I64, I64, VP], c_int32),
+    "u2gnn_layer_fwd_segb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
+                              VP, I32, VP, I64, VP, VP], c_int32),
+    "u2gnn_layer_bwd_segb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,
+                              POINTER(LayerGrads), VP, I64, VP, I32, VP, I64, VP, VP, VP, VP], c_int32),
     "u2gnn_layer_sizes_seg": ([POINTER(LayerDims), F32, I32, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
                               c_int32),
     "u2gnn_layer_fwd_seg": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,

@@ -95,6 +95,15 @@ def batch_hop_lists(lists, sizes: np.ndarray):
     return rowptr, colidx, np.concatenate([d for _, _, d in lists]).astype(np.int32)
 
 
+def pair_block(lists, n: int, H: int) -> np.ndarray:
+    """One graph's pair types from its ``hop_lists(…, H)``: uint8 [n * n], row-major [node][node], entry (i, j) =
+    min(distance(i, j), H), and H where no path joins i and j -- filled with H, then the listed distances scattered."""
+    counts, cols, dist = lists
+    block = np.full(n * n, H, dtype=np.uint8)
+    block[np.repeat(np.arange(n, dtype=np.int64), counts) * n + cols] = dist
+    return block
+
+
 def check_hops_range(hops) -> int:
     if int(hops) != hops or not 1 <= int(hops) <= 31:
         raise ValueError(f"adjacency: hops must be an integer in [1, 31], got {hops!r}")
@@ -172,6 +181,33 @@ class GraphStore:
         first = np.cumsum(deg) - deg                                 # each row's first entry in the batch's list
         pos = np.repeat(self.nbr_start[gnode] - first, deg) + np.arange(int(deg.sum()), dtype=np.int64)
         return csr_with_self(N, np.repeat(np.arange(N, dtype=np.int64), deg), self.nbr[pos] + np.repeat(rowbase, deg))
+
+    def _pair_block(self, gi: int, H: int) -> np.ndarray:
+        """Graph ``gi``'s pair types (``pair_block``), computed on first use and kept in the store as uint8."""
+        cache = self.__dict__.setdefault("_pair_cache", {}).setdefault(H, {})
+        hit = cache.get(gi)
+        if hit is None:
+            hit = cache[gi] = pair_block(self._hop_lists(gi, H), int(self.n_nodes[gi]), H)
+        return hit
+
+    def distances(self, graph_ids: Sequence[int], H: int, out=None):
+        """(pair_off int64 [B+1], etype int32 [sum n_b^2]): the pair types of the batch ``graph_ids`` in packed order --
+        what attention="graphs" with ``distances=H`` (1 <= H <= 31) indexes its hop_bias tables with.  Graph b of the
+        batch owns the entries pair_off[b] .. pair_off[b+1]-1, row-major [n_b][n_b]: entry pair_off[b] + (i - lo) *
+        n_b + (j - lo) is min(shortest-path distance of rows i and j, H), and H when no path joins them (0 on the
+        diagonal).  A graph's block does not depend on the batch: it is computed on first use and kept in the store
+        (uint8), a batch concatenates the blocks.  Deterministic: nothing is drawn from any RNG.
+        out: an int32 array of at least sum n_b^2 entries that receives etype (a page-locked buffer)."""
+        H = check_hops_range(H)
+        ids = np.asarray(graph_ids, dtype=np.int64).reshape(-1)
+        n = self.n_nodes[ids]
+        pair_off = np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum(n * n, out=pair_off[1:])
+        total = int(pair_off[-1])
+        etype = np.empty(total, dtype=np.int32) if out is None else out[:total]
+        for b, g in enumerate(ids):
+            etype[pair_off[b]:pair_off[b + 1]] = self._pair_block(int(g), H)
+        return pair_off, etype
 
     def assemble(self, graph_ids: Sequence[int], num_neighbors: int, rng=np.random,
                  with_input_y: bool = False, gather_x: bool = True, out=None) -> HostBatch:

@@ -24,8 +24,8 @@ from .engine import deep_wgrad as engine_deep_wgrad
 from .engine import (SITE_ATTN, SITE_DROP1, SITE_DROP2, SITE_DROPFF, SITE_HEAD, Dims, LayerParams, PackedLayer,
                      OffPath, encoder_layer_backward, encoder_layer_forward, rup, side_stream_pays, site_seed)
 # (Adjacency, check_hops, ATTENTION_MODES: re-exported, the models, tools and tests import them from here)
-from .pattern import (ATTENTION_MODES, NODES, Adjacency, AttnPattern, DeviceGraphs, check_attention,  # noqa: F401
-                      check_hops)
+from .pattern import (ATTENTION_MODES, NODES, Adjacency, AttnPattern, DeviceGraphs, PairTypes,  # noqa: F401
+                      check_attention, check_distances, check_hops)
 
 
 _IOTA = {}
@@ -75,6 +75,9 @@ class DeviceBatch:
     # the rows' attention pattern (attention="edges"): Adjacency.from_csr(*store.adjacency(graph_ids), N, device), or
     # the same arrays assembled on the GPU (from_store(..., graphs=DeviceGraphs)); the other modes never read it
     adj: Optional[Adjacency] = None
+    # the pair types of attention="graphs" with ``distances``: PairTypes.from_store(store, graph_ids, N, device, H);
+    # the other modes never read it
+    pairs: Optional[PairTypes] = None
 
     def __post_init__(self):
         if self.err is None:
@@ -228,12 +231,17 @@ class EncoderStack:
     U2GNN layers (pytorch_U2GNN_Sup.py:33-39; pytorch_U2GNN_UnSup.py:55-64)."""
 
     def __init__(self, u2gnn_layers, d: int, ff: int, T: int, L: int, prec: str = "fp32", p_enc: float = 0.5,
-                 attention: str = "nodes", hops: Optional[int] = None, hop_bias=None):
-        """hops = H with attention="edges": every layer adds hop_bias()[l][t][distance] to its attention scores;
-        hop_bias: a callable that returns the model's [L, T, H + 1] parameter (read where it lies at each forward)."""
+                 attention: str = "nodes", hops: Optional[int] = None, hop_bias=None,
+                 distances: Optional[int] = None):
+        """hops = H with attention="edges", or distances = H with attention="graphs": every layer adds
+        hop_bias()[l][t][type] to its attention scores, type = the distance of an adjacency entry (hops) or the clipped
+        distance of a pair of the graph (distances); hop_bias: a callable that returns the model's [L, T, H + 1]
+        parameter (read where it lies at each forward)."""
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
         self.attention = check_attention(attention)
         self.hops, self.hop_bias = check_hops(hops, attention), hop_bias
+        self.distances = check_distances(distances, attention, hops)
+        self.n_types = (self.hops or self.distances or 0) + 1   # the width of a hop_bias table (1: no tables)
         self.packed = None
         # Python orchestration only: the three-pass attention forward where the fused kernel would run
         # (tools/prec_train_probe.py)
@@ -247,7 +255,7 @@ class EncoderStack:
         """The stack of a model module; encoder dropout is hard-coded to 0.5 (pytorch_U2GNN_Sup.py:20)."""
         return cls(module.u2gnn_layers, module.feature_dim_size, module.ff_hidden_size, module.num_self_att_layers,
                    module.num_U2GNN_layers, precision, 0.5, getattr(module, "attention", "nodes"),
-                   getattr(module, "hops", None), lambda: module.hop_bias)
+                   getattr(module, "hops", None), lambda: module.hop_bias, getattr(module, "distances", None))
 
     def layer_params(self, l, t) -> LayerParams:
         return LayerParams.from_encoder_layer(self.layers[l].layers[t])
@@ -281,7 +289,19 @@ class EncoderStack:
                 raise ValueError("attention='graphs' needs every graph's nodes as consecutive rows: graph_pool row g "
                                  "must hold the columns rowptr[g] .. rowptr[g+1]-1 and colidx must be 0..N-1 in order "
                                  "(DeviceBatch.from_offsets / from_store build such batches)")
-            return AttnPattern.segments(b.rowptr[:b.B + 1].contiguous()), 1, b.idx_stride
+            pairs = None
+            if self.distances:
+                pairs = b.pairs
+                if pairs is None:
+                    raise ValueError("distances needs the batch's pair types: set DeviceBatch.pairs = "
+                                     "PairTypes.from_store(store, graph_ids, N, device, H) (reference-style tensor "
+                                     "inputs carry no edges)")
+                if pairs.N != b.N or pairs.pair_off.numel() != b.B + 1:
+                    raise ValueError(f"distances: the pair types are over {pairs.N} rows in "
+                                     f"{pairs.pair_off.numel() - 1} graphs, the batch has {b.N} in {b.B}")
+                if pairs.n_types > self.distances + 1:
+                    raise ValueError(f"distances={self.distances}: the pair types go up to {pairs.n_types - 1}")
+            return AttnPattern.segments(b.rowptr[:b.B + 1].contiguous(), pairs), 1, b.idx_stride
         if mode == "edges":
             # the "nodes" path with every row attending over its row of the batch's adjacency (b.adj, on the device)
             if b.adj is None:
@@ -298,16 +318,25 @@ class EncoderStack:
             return AttnPattern.csr(b.adj), 1, b.idx_stride
         return NODES, 1, b.idx_stride
 
+    @staticmethod
+    def _entry_types(pattern):
+        """The pattern's entry types (int32, one per bias value): an adjacency's distances under ``hops``, the pair
+        types under ``distances``."""
+        return pattern.what.etype if pattern.kind == "csr" else pattern.pairs.etype
+
     def forward(self, b: "DeviceBatch", train: bool, need_ctx: bool, seed: int):
         """Returns (outs, ctx): outs[l] = padded [Np, dp] slot-0 output of U2GNN layer l."""
         pattern, W, stride = self._pattern(b)
-        # hops: the per-entry bias of all L * T layers, expanded from the tables in one launch.  The tables are read
-        # where the parameter lies (the flat buffer under a trainer), so a replayed HIP graph sees Adam's updates
-        bias_all = None
-        if self.hops:
-            tables = self.hop_bias().detach().view(self.L * self.T, self.hops + 1)
-            bias_all = torch.empty(self.L * self.T, rup(pattern.nnz, 4), device=tables.device, dtype=torch.float32)
-            K.bias_expand(tables, b.adj.etype, bias_all)
+        # hops / distances: the bias of all L * T layers per entry type, expanded from the tables in one launch.  The
+        # tables are read where the parameter lies (the flat buffer under a trainer), so a replayed HIP graph sees
+        # Adam's updates
+        bias_all, n_bias = None, 0
+        if self.n_types > 1:
+            etype = self._entry_types(pattern)
+            n_bias = etype.numel()
+            tables = self.hop_bias().detach().view(self.L * self.T, self.n_types)
+            bias_all = torch.empty(self.L * self.T, rup(n_bias, 4), device=tables.device, dtype=torch.float32)
+            K.bias_expand(tables, etype, bias_all)
         dev = b.X_concat.device
         d, dp = self.d, rup(self.d, 64)
         dims = Dims(b.N, d, self.ff)                                  # the node rows: outs, the heads
@@ -326,7 +355,7 @@ class EncoderStack:
                     X, c = native.layer_forward(X, self.packed[l][t], self.layer_params(l, t), ldims, train, seeds,
                                                 need_ctx, self.prec, self.p_enc, deep_wgrad=engine_deep_wgrad(),
                                                 pattern=pattern, bias=None if bias_all is None else
-                                                bias_all[l * self.T + t, :pattern.nnz])
+                                                bias_all[l * self.T + t, :n_bias])
                 else:
                     X, c = encoder_layer_forward(X, self.packed[l][t], self.layer_params(l, t), dims, train, seeds,
                                                  need_ctx, self.prec, self.p_enc, three_pass=self.three_pass)
@@ -341,7 +370,8 @@ class EncoderStack:
                 Xn = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
                 K.gather_rows(X, b.input_x, stride, Xn, R, Rp, d, dp, b.err)
                 X = Xn
-        return outs, {"dims": dims, "layers": lctxs, "batch": b, "ldims": ldims, "stride": stride, "slot0": slot0}
+        return outs, {"dims": dims, "layers": lctxs, "batch": b, "ldims": ldims, "stride": stride, "slot0": slot0,
+                      "pattern": pattern}
 
     def _layer_grads_done(self, pre: str, off: OffPath, need_dx: bool) -> None:
         """Hand a layer's finished parameter-gradient region to ``grad_ready`` with a stream ordered after
@@ -366,10 +396,13 @@ class EncoderStack:
         ldims, stride, slot0 = ctx["ldims"], ctx["stride"], ctx["slot0"]
         dnext = None
         off = OffPath(b.input_x.device, enabled=side_stream_pays(ldims))
-        # hops: every layer leaves dL/dbias of its entries in its row; one reduction to the tables after the last layer
-        dbias_all = None
-        if self.hops:
-            dbias_all = torch.empty(self.L * self.T, rup(b.adj.nnz, 4), device=b.input_x.device, dtype=torch.float32)
+        # hops / distances: every layer leaves dL/dbias of its entries in its row; one reduction to the tables after
+        # the last layer
+        dbias_all, etype = None, None
+        if self.n_types > 1:
+            etype = self._entry_types(ctx["pattern"])
+            dbias_all = torch.empty(self.L * self.T, rup(etype.numel(), 4), device=b.input_x.device,
+                                    dtype=torch.float32)
         for l in reversed(range(self.L)):
             dX = ext_grad(l)                                     # [Np, dp] node rows
             if dnext is not None:                                # re-gather of the next U2GNN layer
@@ -388,14 +421,14 @@ class EncoderStack:
                                                self.prec, side=off.side, deep_wgrad=engine_deep_wgrad(),
                                                need_dx=need_dx,
                                                dbias=None if dbias_all is None else
-                                               dbias_all[l * self.T + t, :b.adj.nnz])
+                                               dbias_all[l * self.T + t, :etype.numel()])
                 else:
                     dX = encoder_layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, ldims,
                                                 self.prec, off=off, need_dx=need_dx)
                 self._layer_grads_done(pre, off, need_dx)
             dnext = dX
         if dbias_all is not None:
-            K.bias_table_grad(dbias_all, b.adj.etype, grads["hop_bias"].view(self.L * self.T, self.hops + 1))
+            K.bias_table_grad(dbias_all, etype, grads["hop_bias"].view(self.L * self.T, self.n_types))
         off.join()   # parameter gradients complete before the caller's optimizer reads them
         return dnext
 

@@ -300,6 +300,53 @@ def segment_attn_bwd(QKV, dp, seg_offsets, O, dO, stats, p, seed, q_scale, dQKV,
           "u2gnn_segment_attn_bwd")
 
 
+def _pair_bias(pair_off, bias, dbias, seg_offsets, what):
+    """The per-pair bias of a segments call: pair_off int64 [n_seg + 1], bias / dbias float32 of one length (n_pairs,
+    returned), all contiguous on the device; dbias only with a bias."""
+    if bias is None:
+        if dbias is not None:
+            raise _lib.U2GNNNativeError(f"{what}: dbias given without a bias")
+        return 0
+    if pair_off is None or pair_off.dtype != torch.int64 or not pair_off.is_contiguous() or pair_off.dim() != 1 \
+            or pair_off.numel() != seg_offsets.numel():
+        raise _lib.U2GNNNativeError(f"{what}: pair_off is a contiguous int64 device tensor [n_seg + 1]")
+    for t, name in ((bias, "bias"), (dbias, "dbias")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or t.numel() < 1
+                              or t.numel() != bias.numel()):
+            raise _lib.U2GNNNativeError(f"{what}: {name} is a contiguous float32 device tensor of n_pairs entries")
+    return bias.numel()
+
+
+def segment_attn_fwd_bias(QKV, dp, seg_offsets, pair_off, bias, O, stats, p, seed, N, rows_pad):
+    """segment_attn_fwd with the score of row i and key j of segment g = Qs_i . K_j + bias[pair_off[g] + (i - lo) *
+    n_g + (j - lo)]: bias holds every segment's [n_g, n_g] block row-major, n_pairs floats; None: the plain call."""
+    _dev(QKV, seg_offsets, pair_off, bias, O, stats)
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous():
+        raise _lib.U2GNNNativeError("segment offsets: a contiguous int64 device tensor")
+    n_pairs = _pair_bias(pair_off, bias, None, seg_offsets, "segment_attn_fwd_bias")
+    check(hip_lib().u2gnn_segment_attn_fwd_bias(_p(QKV), QKV.stride(0), int(dp), _p(seg_offsets),
+                                                seg_offsets.numel() - 1, _p(pair_off), n_pairs, _p(bias), _p(O),
+                                                O.stride(0), _p(stats), float(p), int(seed), int(N), int(rows_pad),
+                                                _s()), "u2gnn_segment_attn_fwd_bias")
+
+
+def segment_attn_bwd_bias(QKV, dp, seg_offsets, pair_off, bias, O, dO, stats, p, seed, q_scale, dQKV, dbias, N,
+                          rows_pad):
+    """segment_attn_bwd under the forward's bias; dbias (n_pairs floats, or None) receives dL/dbias = dS per pair."""
+    _dev(QKV, seg_offsets, pair_off, bias, O, dO, stats, dQKV, dbias)
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous():
+        raise _lib.U2GNNNativeError("segment offsets: a contiguous int64 device tensor")
+    if O.stride(0) != dO.stride(0):
+        raise _lib.U2GNNNativeError("O and dO share one leading dimension")
+    n_pairs = _pair_bias(pair_off, bias, dbias, seg_offsets, "segment_attn_bwd_bias")
+    ws = torch.empty(int(rows_pad), device=QKV.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_segment_attn_bwd_bias(_p(QKV), QKV.stride(0), int(dp), _p(seg_offsets),
+                                                seg_offsets.numel() - 1, _p(pair_off), n_pairs, _p(bias), _p(O), _p(dO),
+                                                dO.stride(0), _p(stats), float(p), int(seed), float(q_scale), _p(dQKV),
+                                                dQKV.stride(0), _p(ws), _p(dbias), int(N), int(rows_pad), _s()),
+          "u2gnn_segment_attn_bwd_bias")
+
+
 def _csr(adjacency, *tensors):
     """The u2gnn_csr_attn of a pattern.Adjacency whose arrays live on the tensors' device (checked by its pattern)."""
     return AttnPattern.csr(adjacency).c_args(tensors[0].device)[2]

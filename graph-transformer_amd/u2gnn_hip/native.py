@@ -123,15 +123,21 @@ def _stream(s=None):
 
 
 def _entry_bias(t, pattern, dev, what):
-    """The pointer of a neighbour attention layer's per-entry bias (or its gradient): pattern.nnz contiguous
-    float32 on the layer's device; None: NULL."""
+    """The pointer of a layer's attention bias (or its gradient): contiguous float32 on the layer's device, one per
+    entry of a csr pattern's adjacency (pattern.nnz) or per pair of a segments pattern's pair types
+    (pattern.pairs.n_pairs); None: NULL."""
     if t is None:
         return None
-    if (pattern.kind != "csr" or not t.is_cuda or t.device != dev or t.dtype != torch.float32
-            or not t.is_contiguous() or t.numel() != pattern.nnz):
-        raise _lib.U2GNNNativeError(f"{what}: a contiguous float32 tensor of the adjacency's nnz entries on the "
-                                    "layer's device (and only with an adjacency)")
+    n = pattern.nnz if pattern.kind == "csr" else pattern.pairs.n_pairs if pattern.pairs is not None else -1
+    if n < 1 or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        raise _lib.U2GNNNativeError(f"{what}: a contiguous float32 tensor on the layer's device, one value per entry "
+                                    "of the adjacency (csr) or per pair of the pair types (segments with pairs)")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _pair_biased(pattern, bias) -> bool:
+    """Whether the call goes through u2gnn_layer_*_segb: a segments pattern that carries pairs, with a bias."""
+    return bias is not None and pattern.kind == "segments" and pattern.pairs is not None
 
 
 def _shared_args(dims, packed, p, prec, deep_wgrad, pattern, p_drop, seeds, X):
@@ -146,8 +152,9 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
                   prec: str, p_enc: float, deep_wgrad: bool = True, pattern: AttnPattern = NODES, bias=None):
     """pattern (pattern.AttnPattern): the rows every row of X attends over -- NODES: all dims.N rows; window(W): its
     node's W token rows (dims.N = nodes * W); segments(offsets): the rows of its own segment (per-graph attention);
-    csr(adjacency): the columns of its CSR row (neighbour attention).  bias (f32 device [pattern.nnz], only with a
-    csr pattern): added to the entries' scores before the softmax."""
+    csr(adjacency): the columns of its CSR row (neighbour attention).  bias (f32 device): added to the scores before
+    the softmax -- [pattern.nnz] per entry of a csr pattern, or [pattern.pairs.n_pairs] per pair of a segments pattern
+    that carries pairs (PairTypes' packed order)."""
     pd = p_enc if train else 0.0
     cb, fb, _ = sizes(dims.N, dims.d, dims.ff, prec, pd, deep_wgrad, pattern)
     dev = X.device
@@ -155,6 +162,12 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
     buf = torch.empty(cb, device=dev, dtype=torch.uint8) if need_ctx else None
     ws = torch.empty(max(256, fb + (0 if need_ctx else cb)), device=dev, dtype=torch.uint8)
     head = _shared_args(dims, packed, p, prec, deep_wgrad, pattern, pd, seeds, X)
+    if _pair_biased(pattern, bias):
+        check(hip_lib().u2gnn_layer_fwd_segb(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
+                                             ws.data_ptr(), ws.numel(), *pattern.c_args(dev)[:2],
+                                             *pattern.pair_args(dev), _entry_bias(bias, pattern, dev, "bias"),
+                                             _stream()), "u2gnn_layer_fwd_segb")
+        return X2, NativeCtx(X, buf, pd, dict(seeds), pattern, bias) if need_ctx else None
     check(hip_lib().u2gnn_layer_fwd_csrb(*head, X2.data_ptr(), buf.data_ptr() if buf is not None else None, cb,
                                          ws.data_ptr(), ws.numel(), *pattern.c_args(dev),
                                          _entry_bias(bias, pattern, dev, "bias"), _stream()), "u2gnn_layer_fwd_csrb")
@@ -164,8 +177,8 @@ def layer_forward(X: torch.Tensor, packed, p, dims, train: bool, seeds: Dict[int
 def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: str,
                    side: Optional["torch.cuda.Stream"] = None, deep_wgrad: bool = True,
                    need_dx: bool = True, dbias=None) -> Optional[torch.Tensor]:
-    """The forward's pattern and bias are taken from ctx; dbias (f32 device [pattern.nnz], only for a forward with a
-    bias) receives the bias's gradient."""
+    """The forward's pattern and bias are taken from ctx; dbias (f32 device, the bias's length, only for a forward with
+    a bias) receives the bias's gradient."""
     if dbias is not None and ctx.bias is None:
         raise _lib.U2GNNNativeError("layer_backward: dbias given for a forward that ran without a bias")
     pattern = ctx.pattern
@@ -175,11 +188,20 @@ def layer_backward(dX2: torch.Tensor, ctx: NativeCtx, packed, p, g, dims, prec: 
     ws = torch.empty(max(256, bb), device=dev, dtype=torch.uint8)
     head = _shared_args(dims, packed, p, prec, deep_wgrad, pattern, ctx.p_drop, ctx.seeds, ctx.X)
     gg = LayerGrads(*[getattr(g, k).data_ptr() for k in _lib._PKEYS])
-    check(hip_lib().u2gnn_layer_bwd_csrb(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
-                                         dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(),
-                                         ws.numel(), *pattern.c_args(dev), _entry_bias(ctx.bias, pattern, dev, "bias"),
-                                         _entry_bias(dbias, pattern, dev, "dbias"), _stream(),
-                                         _stream(side) if side is not None else None), "u2gnn_layer_bwd_csrb")
+    if _pair_biased(pattern, ctx.bias):
+        check(hip_lib().u2gnn_layer_bwd_segb(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
+                                             dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(),
+                                             ws.numel(), *pattern.c_args(dev)[:2], *pattern.pair_args(dev),
+                                             _entry_bias(ctx.bias, pattern, dev, "bias"),
+                                             _entry_bias(dbias, pattern, dev, "dbias"), _stream(),
+                                             _stream(side) if side is not None else None), "u2gnn_layer_bwd_segb")
+    else:
+        check(hip_lib().u2gnn_layer_bwd_csrb(*head, ctx.buf.data_ptr(), cb, dX2.data_ptr(),
+                                             dX.data_ptr() if need_dx else None, ctypes.byref(gg), ws.data_ptr(),
+                                             ws.numel(), *pattern.c_args(dev),
+                                             _entry_bias(ctx.bias, pattern, dev, "bias"),
+                                             _entry_bias(dbias, pattern, dev, "dbias"), _stream(),
+                                             _stream(side) if side is not None else None), "u2gnn_layer_bwd_csrb")
     if side is not None:
         for t in (ws, ctx.buf, ctx.X, dX2):
             t.record_stream(side)

@@ -1,6 +1,7 @@
-"""Which rows a row attends over, said once: the model's ``attention`` / ``hops`` keywords (check_attention,
-check_hops), the batch's device-resident adjacency (Adjacency) and the value every layer call takes (AttnPattern),
-which alone turns a pattern into the arguments of the C ABI (u2gnn_layer_*_csrb, u2gnn_csr_attn_*)."""
+"""Which rows a row attends over, said once: the model's ``attention`` / ``hops`` / ``distances`` keywords
+(check_attention, check_hops, check_distances), the batch's device-resident adjacency (Adjacency) or pair types
+(PairTypes) and the value every layer call takes (AttnPattern), which alone turns a pattern into the arguments of the
+C ABI (u2gnn_layer_*_csrb, u2gnn_layer_*_segb, u2gnn_csr_attn_*)."""
 from __future__ import annotations
 
 import ctypes
@@ -12,6 +13,7 @@ import torch
 from ._lib import BIAS_TYPES_MAX, U2GNNNativeError
 
 ATTENTION_MODES = ("nodes", "neighbors", "graphs", "edges")
+BIAS_ENTRIES_MAX = 4096 * 112 * 256   # the entries u2gnn_bias_table_grad reduces in one call (u2gnn_hip.h)
 
 
 def check_attention(name: str) -> str:
@@ -30,6 +32,84 @@ def check_hops(hops, attention: str) -> Optional[int]:
     if int(hops) != hops or not 1 <= int(hops) <= BIAS_TYPES_MAX - 1:
         raise ValueError(f"hops must be an integer in [1, {BIAS_TYPES_MAX - 1}], got {hops!r}")
     return int(hops)
+
+
+def check_distances(distances, attention: str, hops=None) -> Optional[int]:
+    """The ``distances`` keyword of the models: None (off) or an H in [1, 31], only with attention="graphs" and never
+    together with ``hops``."""
+    if distances is None:
+        return None
+    if attention != "graphs":
+        raise ValueError(f"distances needs attention='graphs', got attention={attention!r}")
+    if hops is not None:
+        raise ValueError("distances and hops exclude each other (hops is attention='edges', distances 'graphs')")
+    if int(distances) != distances or not 1 <= int(distances) <= BIAS_TYPES_MAX - 1:
+        raise ValueError(f"distances must be an integer in [1, {BIAS_TYPES_MAX - 1}], got {distances!r}")
+    return int(distances)
+
+
+class PairTypes:
+    """The pair types of attention="graphs" with ``distances`` on the device: graph b of the batch owns the entries
+    pair_off[b] .. pair_off[b+1]-1 of etype, its [n_b, n_b] block row-major (GraphStore.distances): etype[pair_off[b] +
+    (i - lo) n_b + (j - lo)] is the clipped shortest-path distance of rows i and j, the index into the model's hop_bias
+    tables.  pair_off int64 [B+1], etype int32 [n_pairs], n_types = max(etype) + 1; N: the batch's rows."""
+    __slots__ = ("N", "n_pairs", "pair_off", "etype", "n_types")
+
+    def __init__(self, N, pair_off, etype, n_types):
+        self.N, self.n_pairs, self.n_types = int(N), int(etype.numel()), int(n_types)
+        self.pair_off, self.etype = pair_off, etype
+
+    @staticmethod
+    def _check(pair_off, etype, N):
+        po = np.ascontiguousarray(np.asarray(pair_off), dtype=np.int64).reshape(-1)
+        et = np.asarray(etype).reshape(-1)
+        if int(N) < 1 or po.shape[0] < 2:
+            raise ValueError("pair types: at least one row and one graph")
+        if po[0] != 0 or po[-1] != et.shape[0] or (np.diff(po) < 0).any():
+            raise ValueError("pair types: pair_off must start at 0, never decrease and end at len(etype)")
+        if not 1 <= et.shape[0] <= BIAS_ENTRIES_MAX:
+            raise ValueError(f"pair types: between 1 and {BIAS_ENTRIES_MAX} pairs, got {et.shape[0]}")
+        lo, hi = int(et.min()), int(et.max())
+        if lo < 0 or hi >= BIAS_TYPES_MAX:
+            raise ValueError(f"pair types: a type outside [0, {BIAS_TYPES_MAX})")
+        return po, et, hi + 1
+
+    @staticmethod
+    def _send(po, et, N, n_types, device, staged=None) -> "PairTypes":
+        """Both arrays leave from page-locked memory without blocking (staged: etype is already a view of ``staged``,
+        a page-locked int32 tensor)."""
+        dev = torch.device(device)
+        pin = dev.type == "cuda"
+        if staged is None:
+            staged = torch.empty(et.shape[0], dtype=torch.int32, pin_memory=pin)   # the caching host allocator keeps a
+            staged.numpy()[:] = et                                                 # block until its copy is done
+        hp = torch.empty(po.shape[0], dtype=torch.int64, pin_memory=pin)
+        hp.numpy()[:] = po
+        return PairTypes(N, hp.to(dev, non_blocking=True), staged[:et.shape[0]].to(dev, non_blocking=True), n_types)
+
+    @staticmethod
+    def from_arrays(pair_off, etype, N: int, device="cuda") -> "PairTypes":
+        """Validates on the host (ValueError: pair_off not starting at 0, decreasing or not ending at len(etype); a type
+        outside [0, 32); no pair, or more than u2gnn_bias_table_grad reduces) and moves both arrays to ``device``
+        (etype as int32)."""
+        po, et, n_types = PairTypes._check(pair_off, etype, N)
+        return PairTypes._send(po, et, N, n_types, device)
+
+    @staticmethod
+    def from_store(store, graph_ids, N: int, device="cuda", H: int = 1) -> "PairTypes":
+        """The pair types of a batch of ``store``'s graphs (``store.distances(graph_ids, H)``: cached per-graph blocks,
+        concatenated straight into a page-locked buffer), validated as ``from_arrays``."""
+        ids = np.asarray(graph_ids, dtype=np.int64).reshape(-1)
+        n = np.asarray(store.n_nodes, dtype=np.int64)[ids]
+        total = int((n * n).sum())
+        if int(n.sum()) != int(N):
+            raise ValueError(f"pair types: the store gives the batch {int(n.sum())} rows, the batch has {int(N)}")
+        if not 1 <= total <= BIAS_ENTRIES_MAX:
+            raise ValueError(f"pair types: between 1 and {BIAS_ENTRIES_MAX} pairs, got {total}")
+        staged = torch.empty(total, dtype=torch.int32, pin_memory=torch.device(device).type == "cuda")
+        po, et = store.distances(ids, H, out=staged.numpy())
+        po, et, n_types = PairTypes._check(po, et, N)
+        return PairTypes._send(po, et, N, n_types, device, staged)
 
 
 class Adjacency:
@@ -270,18 +350,21 @@ class AttnPattern:
 
     * ``NODES``: every row over all rows of the layer;
     * ``window(W)``: within each node's window of W token rows (the layer has nodes * W rows);
-    * ``segments(offsets)``: over the rows of its own segment (per-graph attention); offsets: int64 device
-      [n_seg + 1] row offsets;
+    * ``segments(offsets, pairs=None)``: over the rows of its own segment (per-graph attention); offsets: int64 device
+      [n_seg + 1] row offsets; pairs: the segments' PairTypes, for layers that add a per-pair bias to their scores;
     * ``csr(adjacency)``: over the columns of its row of an Adjacency (neighbour attention).
 
     One payload per kind, so no two can be combined.  ``W`` and ``nnz`` are 0 for the kinds without them; ``key`` is
-    what the layer's buffer sizes depend on (hashable: native.sizes caches by it)."""
-    __slots__ = ("kind", "what", "W", "nnz", "key", "_c")
+    what the layer's buffer sizes depend on (hashable: native.sizes caches by it) -- never on ``pairs``: nothing of a
+    bias lives in the layer's buffers, and the pair count travels on its own (``pair_args``)."""
+    __slots__ = ("kind", "what", "W", "nnz", "key", "pairs", "_c")
 
-    def __init__(self, kind: str, what=None):
+    def __init__(self, kind: str, what=None, pairs=None):
         W, nnz = what if kind == "window" else 0, getattr(what, "nnz", 0) if kind == "csr" else 0
+        if pairs is not None and kind != "segments":
+            raise ValueError("pair types go with a segments pattern")
         for name, v in (("kind", kind), ("what", what), ("W", W), ("nnz", nnz), ("key", (W, kind == "segments", nnz)),
-                        ("_c", None)):
+                        ("pairs", pairs), ("_c", None)):
             object.__setattr__(self, name, v)
 
     def __setattr__(self, name, value):
@@ -292,8 +375,8 @@ class AttnPattern:
         return AttnPattern("window", int(W))
 
     @staticmethod
-    def segments(offsets: torch.Tensor) -> "AttnPattern":
-        return AttnPattern("segments", offsets)
+    def segments(offsets: torch.Tensor, pairs: Optional[PairTypes] = None) -> "AttnPattern":
+        return AttnPattern("segments", offsets, pairs)
 
     @staticmethod
     def csr(adjacency: Adjacency) -> "AttnPattern":
@@ -308,6 +391,18 @@ class AttnPattern:
             c = (device, self._c_args(device))
             object.__setattr__(self, "_c", c)
         return c[1]
+
+    def pair_args(self, device):
+        """(pair offsets pointer, pair count) as u2gnn_layer_fwd_segb / _bwd_segb take them.  U2GNNNativeError unless
+        this is a segments pattern with PairTypes on ``device``, one offset per segment bound."""
+        pt = self.pairs
+        self.c_args(device)
+        if (self.kind != "segments" or not isinstance(pt, PairTypes) or pt.n_pairs < 1 or not pt.pair_off.is_cuda
+                or pt.pair_off.device != device or pt.pair_off.dtype != torch.int64 or not pt.pair_off.is_contiguous()
+                or pt.pair_off.numel() != self.what.numel()):
+            raise U2GNNNativeError("pairs: a segments pattern with PairTypes on the layer's device, pair_off int64 "
+                                   "[n_seg + 1]")
+        return ctypes.c_void_p(pt.pair_off.data_ptr()), pt.n_pairs
 
     def _c_args(self, device):
         t = self.what

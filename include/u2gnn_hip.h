@@ -564,6 +564,25 @@ int u2gnn_segment_attn_bwd(const float *QKV, int64_t ldq, int32_t dp, const int6
                            const float *O, const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed,
                            float q_scale, float *dQKV, int64_t ldg, float *delta_ws, int64_t N, int64_t rows_pad,
                            void *stream);
+/* The same two calls with an additive bias per (query, key) pair of a segment (ABI 19 grew by these entry points,
+ * nothing else changed): the score of row i and key j of segment g is Qs_i . K_j + bias[e], e = pair_off[g] +
+ * (i - lo) * (hi - lo) + (j - lo) with [lo, hi) the segment's CLAMPED row range -- segment g's pairs are the
+ * consecutive floats bias[pair_off[g] ..], row-major [query][key].  pair_off: DEVICE int64 [n_seg+1], never read by
+ * the host; bias: n_pairs DEVICE floats (finite; not scanned).  Any pair_off content is memory-safe: an entry id
+ * outside [0, n_pairs) reads a bias of 0 and is not written to dbias.  The backward recomputes P with the same bias
+ * and, when dbias is not NULL, also stores dL/dbias[e] = dS_ij into dbias (n_pairs floats; every pair of a covered
+ * row once, no atomics, entries that are no pair of the batch are left as they were).  Tiles and summation order
+ * are those of the plain calls: a zero bias gives their bits.  bias == NULL (and dbias == NULL) is
+ * u2gnn_segment_attn_fwd / _bwd exactly (those forward here; pair_off and n_pairs are then ignored); dbias without
+ * bias, bias without pair_off, or n_pairs < 1 with a bias: U2GNN_E_ARG before anything is launched. */
+int u2gnn_segment_attn_fwd_bias(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                                const int64_t *pair_off, int64_t n_pairs, const float *bias, float *O, int64_t ldo,
+                                float *stats, float p, uint64_t seed, int64_t N, int64_t rows_pad, void *stream);
+int u2gnn_segment_attn_bwd_bias(const float *QKV, int64_t ldq, int32_t dp, const int64_t *seg_offsets, int32_t n_seg,
+                                const int64_t *pair_off, int64_t n_pairs, const float *bias, const float *O,
+                                const float *dO, int64_t ldo, const float *stats, float p, uint64_t seed, float q_scale,
+                                float *dQKV, int64_t ldg, float *delta_ws, float *dbias, int64_t N, int64_t rows_pad,
+                                void *stream);
 
 /* ---- neighbour ("edges" mode) attention: row i attends over the columns of its CSR row -- the batch's adjacency
  * plus the diagonal when the caller builds it so (u2gnn_hip.core.Adjacency).  The conventions of
@@ -741,6 +760,22 @@ int u2gnn_layer_bwd_seg(const u2gnn_layer_dims *dims, const u2gnn_layer_params *
                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
                         int32_t n_seg, void *stream, void *side_stream);
+/* The _seg calls with the layer's per-pair attention bias (u2gnn_segment_attn_*_bias; ABI 19 grew by these entry
+ * points, nothing else changed): pair_off (DEVICE int64 [n_seg+1]), n_pairs and bias (n_pairs device floats), and in
+ * the backward dbias (n_pairs floats, caller-owned, may be NULL), which receives dL/dbias.  The sizes are
+ * u2gnn_layer_sizes_seg's: nothing of the bias lives in ctx or the workspaces.  bias == NULL and dbias == NULL is the
+ * _seg call exactly (the _seg calls forward here).  dbias without bias, bias without pair_off, n_pairs < 1 with a
+ * bias, a bias without segments or together with dims->window: U2GNN_E_ARG before anything is launched.  (A bias
+ * with a CSR is u2gnn_layer_*_csrb below, which keeps refusing a bias without a CSR.) */
+int u2gnn_layer_fwd_segb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, float *X2, void *ctx, int64_t ctx_bytes, void *ws, int64_t ws_bytes,
+                         const int64_t *seg_offsets, int32_t n_seg, const int64_t *pair_off, int64_t n_pairs,
+                         const float *bias, void *stream);
+int u2gnn_layer_bwd_segb(const u2gnn_layer_dims *dims, const u2gnn_layer_params *w, const u2gnn_layer_seeds *s,
+                         const float *X, const void *ctx, int64_t ctx_bytes, const float *dX2, float *dX,
+                         const u2gnn_layer_grads *g, void *ws, int64_t ws_bytes, const int64_t *seg_offsets,
+                         int32_t n_seg, const int64_t *pair_off, int64_t n_pairs, const float *bias, float *dbias,
+                         void *stream, void *side_stream);
 /* The same three calls with neighbour attention (u2gnn_csr_attn_*; ABI 18 grew by these entry points, nothing else
  * changed): every row attends over the columns of its CSR row.  The layer takes the generic route (in-projection
  * GEMM -> CSR attention -> out-projection and tail), the ctx arena holds the row statistics in place of the

@@ -7,7 +7,18 @@
     in one HIP graph) against their algorithmic work: 2 * sum_g n_g^2 * dp FLOP per product (2 products forward, 5
     backward: P is recomputed) and the QKV / O / dO / dQKV bytes.
 
-Prints one JSON line.  Usage: python tools/graphs_mode_bench.py [--steps 24] [--warmup 5] [--batches 4]"""
+With --distances H (attention="graphs" with a learned bias per shortest-path distance) it measures that mode instead,
+per setting (c4: the same synthetic graphs as a GraphStore; mutag: MUTAG from dataset/ at batch_size 64):
+
+  * the segment kernels alone, without bias and as the BIAS instantiation at a zero table (equal arithmetic), beside the
+    CSR kernels over the --csr_hops adjacency of the same batch with a zero bias (on C4 two hops reach every node: the
+    same pairs), u2gnn_bias_expand and u2gnn_bias_table_grad for the step's T tables;
+  * the eager step under graphs, graphs + distances=H and edges + hops, median over rotating blocks in one process;
+  * the host cost of PairTypes.from_store per batch with cached blocks (host clock to the return of the call, and to a
+    device synchronise after it).
+
+Prints one JSON line.  Usage: python tools/graphs_mode_bench.py [--steps 24] [--warmup 5] [--batches 4]
+       python tools/graphs_mode_bench.py --distances 3 [--settings c4,mutag] [--csr_hops 2]"""
 import argparse
 import json
 import math
@@ -72,6 +83,143 @@ def kernel_figures(offsets, d):
             "bwd_mb": round(b_bytes / 1e6, 2), "bwd_gbs": round(b_bytes / bwd / 1e3, 1)}
 
 
+def distance_kernel_figures(offsets, pairs, adj, d, T):
+    """The segment kernels on one batch's layer shape without bias and with a zero bias, the CSR kernels over ``adj``
+    with a zero bias, and the two table kernels over the pair types."""
+    from u2gnn_hip.engine import row_pad, rup
+    N, dp = int(offsets[-1]), rup(d, 64)
+    Np = row_pad(N)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    QKV = torch.randn(Np, 3 * dp, device="cuda", generator=g)
+    QKV[:, :dp] *= 1 / math.sqrt(dp)
+    QKV[N:] = 0
+    dO = torch.randn(Np, dp, device="cuda", generator=g)
+    O, stats = torch.empty(Np, dp, device="cuda"), torch.empty(Np, 2, device="cuda")
+    dQKV = torch.empty(Np, 3 * dp, device="cuda")
+    off = torch.as_tensor(np.asarray(offsets), dtype=torch.int64).cuda()
+    qs = 1 / math.sqrt(d)
+    po, n = pairs.pair_off, pairs.n_pairs
+    zero, db = torch.zeros(n, device="cuda"), torch.empty(n, device="cuda")
+    zc, dbc = torch.zeros(adj.nnz, device="cuda"), torch.empty(adj.nnz, device="cuda")
+    tables = torch.zeros(T, pairs.n_types, device="cuda")
+    rows = torch.empty(T, rup(n, 4), device="cuda")
+    dt = torch.empty(T, pairs.n_types, device="cuda")
+    t = {
+        "fwd_us": graph_time_us(lambda: K.segment_attn_fwd(QKV, dp, off, O, stats, 0.5, 7, N, Np)),
+        "fwd_zero_bias_us": graph_time_us(lambda: K.segment_attn_fwd_bias(QKV, dp, off, po, zero, O, stats, 0.5, 7, N,
+                                                                          Np)),
+        "bwd_us": graph_time_us(lambda: K.segment_attn_bwd(QKV, dp, off, O, dO, stats, 0.5, 7, qs, dQKV, N, Np)),
+        "bwd_zero_bias_us": graph_time_us(lambda: K.segment_attn_bwd_bias(QKV, dp, off, po, zero, O, dO, stats, 0.5, 7,
+                                                                          qs, dQKV, db, N, Np)),
+        "bwd_zero_bias_no_dbias_us": graph_time_us(lambda: K.segment_attn_bwd_bias(QKV, dp, off, po, zero, O, dO, stats,
+                                                                                   0.5, 7, qs, dQKV, None, N, Np)),
+        "csr_fwd_zero_bias_us": graph_time_us(lambda: K.csr_attn_fwd_bias(QKV, dp, adj, zc, O, stats, 0.5, 7, N, Np)),
+        "csr_bwd_zero_bias_us": graph_time_us(lambda: K.csr_attn_bwd_bias(QKV, dp, adj, zc, O, dO, stats, 0.5, 7, qs,
+                                                                          dQKV, dbc, N, Np)),
+        "expand_us": graph_time_us(lambda: K.bias_expand(tables, pairs.etype, rows)),
+        "table_grad_us": graph_time_us(lambda: K.bias_table_grad(rows, pairs.etype, dt)),
+    }
+    out = {"N": N, "dp": dp, "graphs": len(offsets) - 1, "pairs": n, "csr_nnz": adj.nnz,
+           "bias_mb": round(4 * n / 1e6, 3)}
+    out.update({k: round(v, 2) for k, v in t.items()})
+    out["fwd_bias_over_plain"] = round(t["fwd_zero_bias_us"] / t["fwd_us"], 4)
+    out["bwd_bias_over_plain"] = round(t["bwd_zero_bias_us"] / t["bwd_us"], 4)
+    out["csr_over_segment_fwd"] = round(t["csr_fwd_zero_bias_us"] / t["fwd_zero_bias_us"], 4)
+    out["csr_over_segment_bwd"] = round(t["csr_bwd_zero_bias_us"] / t["bwd_zero_bias_us"], 4)
+    return out
+
+
+def distance_setting(name, store, C, batch_size, k, args):
+    import time
+
+    from pytorch_U2GNN_Sup import TransformerU2GNN
+    from u2gnn_hip.batching import BatchLoader
+    from u2gnn_hip.core import Adjacency, DeviceBatch, PairTypes
+    from u2gnn_hip.train import SupTrainer
+    T, ff, H = 4, 1024, args.distances
+    np.random.seed(123)
+    loader = BatchLoader(store, batch_size, k)
+    host = [loader() for _ in range(args.batches)]
+    batches = []
+    for h in host:
+        b = DeviceBatch.from_offsets(h.input_x, h.offsets, h.X_concat, h.labels, device="cuda")
+        b.pairs = PairTypes.from_store(store, h.graph_ids, b.N, "cuda", H)
+        b.adj = Adjacency.from_store(store, h.graph_ids, b.N, "cuda", hops=args.csr_hops)
+        batches.append(b)
+    d = host[0].X_concat.shape[1]
+    # the host cost per batch, blocks cached (the loop above computed them)
+    ret, synced = [], []
+    for i in range(5 * len(host)):
+        h = host[i % len(host)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pt = PairTypes.from_store(store, h.graph_ids, int(h.offsets[-1]), "cuda", H)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        ret.append((t1 - t0) * 1e3), synced.append((t2 - t0) * 1e3)
+        del pt
+    variants = [("graphs", dict(attention="graphs")), (f"graphs_d{H}", dict(attention="graphs", distances=H)),
+                (f"edges_h{args.csr_hops}", dict(attention="edges", hops=args.csr_hops))]
+    names = tuple(v[0] for v in variants)
+    trainers = {}
+    for vname, kw in variants:
+        torch.manual_seed(123)
+        m = TransformerU2GNN(d, ff, C, T, 0.5, 1, precision=args.precision, **kw).cuda().train()
+        trainers[vname] = SupTrainer(m, lr=5e-4, max_norm=0.5, seed=123)
+    nb = len(batches)
+    for tr in trainers.values():
+        for i in range(args.warmup):
+            tr.step(batches[i % nb])
+    torch.cuda.synchronize()
+    times = {v: [] for v in names}
+    done, blk = 0, 0
+    while done < args.steps:
+        r = blk % len(names)
+        n = min(args.block, args.steps - done)
+        for vname in names[r:] + names[:r]:
+            for i in range(n):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                trainers[vname].step(batches[(done + i) % nb])
+                e1.record()
+                torch.cuda.synchronize()
+                times[vname].append(e0.elapsed_time(e1))
+        done += n
+        blk += 1
+    med = {v: round(statistics.median(x), 4) for v, x in times.items()}
+    return {"setting": f"{name}: bs {batch_size}, k {k}, d {d}, T {T}, ff {ff}, {args.precision}, {nb} batches, eager "
+                       f"steps, median of {args.steps} per variant in rotating blocks of {args.block}",
+            "step_ms": med, "step_ms_min_max": {v: [round(min(x), 4), round(max(x), 4)] for v, x in times.items()},
+            "distances_over_graphs": round(med[names[1]] / med[names[0]], 4),
+            "distances_over_edges_hops": round(med[names[1]] / med[names[2]], 4),
+            "pairs": [b.pairs.n_pairs for b in batches], "csr_nnz": [b.adj.nnz for b in batches],
+            "pair_types_from_store_ms": {"to_return_median": round(statistics.median(ret), 4),
+                                         "to_device_sync_median": round(statistics.median(synced), 4),
+                                         "min_max_to_sync": [round(min(synced), 4), round(max(synced), 4)],
+                                         "calls": len(ret)},
+            "kernels": [distance_kernel_figures(h.offsets, b.pairs, b.adj, d, T)
+                        for h, b in list(zip(host, batches))[:2]]}
+
+
+def distances_main(args):
+    import util
+    from u2gnn_hip.batching import GraphStore
+    from u2gnn_hip.synthetic import as_graph_store, collab_like
+    out = {"distances": args.distances, "csr_hops": args.csr_hops}
+    for which in args.settings.split(","):
+        if which == "c4":
+            out["c4"] = distance_setting("C4 synthetic as a GraphStore", as_graph_store(collab_like(seed=0)), 3, 64, 16,
+                                         args)
+        elif which == "mutag":
+            graphs, C = util.load_data("MUTAG", False)
+            out["mutag"] = distance_setting("MUTAG", GraphStore(graphs), C, 64, 16, args)
+        else:
+            raise SystemExit(f"unknown setting {which!r}")
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=24, help="timed steps per mode (>= 20)")
@@ -79,8 +227,13 @@ def main():
     ap.add_argument("--batches", type=int, default=4)
     ap.add_argument("--block", type=int, default=4, help="steps per alternation block")
     ap.add_argument("--precision", default="fwdh")
+    ap.add_argument("--distances", type=int, default=0, help="H: measure attention='graphs' with distances=H instead")
+    ap.add_argument("--settings", default="c4,mutag", help="with --distances: which of c4, mutag to run")
+    ap.add_argument("--csr_hops", type=int, default=2, help="with --distances: the edges + hops route beside it")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X: a timing without one would mean nothing"
+    if args.distances:
+        return distances_main(args)
     from pytorch_U2GNN_Sup import TransformerU2GNN
     from u2gnn_hip.batching import BatchLoader
     from u2gnn_hip.core import DeviceBatch
