@@ -63,12 +63,14 @@ parser.add_argument("--distances", default=0, type=int,
                     help="with --attention graphs: every encoder layer adds a learned bias per shortest-path distance "
                          "(clipped at this many bonds, 1..31; unconnected pairs take the last entry) to the scores of "
                          "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
-                         "--adjacency has no effect on it")
+                         "--adjacency says where each batch's distances are searched")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
-                    help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
-                         "from a per-dataset structure kept there (built once at start; a dataset whose structure "
-                         "does not fit falls back to host); host = built on the host for every batch and copied.  "
-                         "Both give the same integers, hence the same losses")
+                    help="where each batch's adjacency (--attention edges) or pair distances (--attention graphs "
+                         "--distances) are built: device = on the GPU from a per-dataset structure kept there (built "
+                         "once at start, the --hops lists and every shortest-path search on the GPU; a dataset whose "
+                         "structure does not fit or that holds a graph above 4096 nodes falls back to host); host = "
+                         "built on the host for every batch and copied.  Both give the same integers, hence the same "
+                         "losses")
 parser.add_argument("--autograd", action="store_true", help="reference loop: autograd + torch Adam/StepLR")
 parser.add_argument("--max_steps", default=0, type=int, help="stop after this many train steps (0 = no limit)")
 parser.add_argument("--world_size", default=1, type=int,
@@ -138,21 +140,24 @@ steps_per_epoch = -(-num_batches_per_epoch // run.world)
 train_X = torch.from_numpy(train_store.X).to(device)
 # --adjacency device: each store's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
 edges = args.attention == "edges"
-graphs_of = {id(s): device_graphs(s, device, args.hops, args.adjacency, log) if edges else None
-             for s in (train_store, test_store)}
+graphs_of = {id(s): device_graphs(s, device, args.hops, args.adjacency, log, distances=args.distances)
+             if edges or args.distances else None for s in (train_store, test_store)}
 
 
 def to_device(hb, store=train_store):
     dg = graphs_of[id(store)]
     if hb.X_concat is None:
-        b = DeviceBatch.from_store(hb, train_X, device=device, graphs=dg)
+        b = DeviceBatch.from_store(hb, train_X, device=device, graphs=dg,
+                                   distances=(args.distances or None) if dg is not None else None)
     else:
         b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
-        if dg is not None:
+        if dg is not None and args.distances:
+            b.pairs = dg.pair_types(hb.graph_ids, args.distances, b.rowptr)
+        elif dg is not None:
             b.adj = dg.adjacency(hb.graph_ids, b.rowptr)
     if edges and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists), from the store
         b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
-    if args.distances:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
+    if args.distances and b.pairs is None:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
         b.pairs = PairTypes.from_store(store, hb.graph_ids, b.N, device, args.distances)
     return b
 

@@ -64,12 +64,15 @@ parser.add_argument("--distances", default=0, type=int,
                     help="with --attention graphs: every encoder layer adds a learned bias per shortest-path distance "
                          "(clipped at this many bonds, 1..31; unconnected pairs take the last entry) to the scores of "
                          "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
-                         "--adjacency has no effect on it.  Not with --world_size > 1, as --hops")
+                         "--adjacency says where each batch's distances are searched.  Not with --world_size > 1, as "
+                         "--hops")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
-                    help="with --attention edges, where each batch's adjacency is built: device = assembled on the GPU "
-                         "from a per-dataset structure kept there (built once at start; a dataset whose structure "
-                         "does not fit falls back to host); host = built on the host for every batch and copied.  "
-                         "Both give the same integers, hence the same losses")
+                    help="where each batch's adjacency (--attention edges) or pair distances (--attention graphs "
+                         "--distances) are built: device = on the GPU from a per-dataset structure kept there (built "
+                         "once at start, the --hops lists and every shortest-path search on the GPU; a dataset whose "
+                         "structure does not fit or that holds a graph above 4096 nodes falls back to host); host = "
+                         "built on the host for every batch and copied.  Both give the same integers, hence the same "
+                         "losses")
 parser.add_argument("--world_size", default=1, type=int,
                     help="data-parallel ranks, one per GPU (started here under torch.distributed.run unless a "
                          "launcher already set WORLD_SIZE; left at 1 under a launcher it takes WORLD_SIZE).  "
@@ -126,7 +129,8 @@ if reddit:
 store = GraphStore(graphs, reddit_tile=4 if reddit else 0)
 store_X = torch.from_numpy(store.X).to(device)
 # --adjacency device: the dataset's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
-store_graphs = device_graphs(store, device, args.hops, args.adjacency, log) if args.attention == "edges" else None
+store_graphs = (device_graphs(store, device, args.hops, args.adjacency, log, distances=args.distances)
+                if args.attention == "edges" or args.distances else None)
 vocab_size = int(store.node_start[-1])
 # native assembly; node features gathered on the GPU from a device-resident copy (DeviceBatch.from_store)
 batch_nodes = BatchLoader(store, args.batch_size, args.num_neighbors, with_input_y=True, gather_x=False)
@@ -160,10 +164,11 @@ def train():
         if args.max_steps and steps_done >= args.max_steps:
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
-        b = DeviceBatch.from_store(hb, store_X, device=device, graphs=store_graphs)
+        b = DeviceBatch.from_store(hb, store_X, device=device, graphs=store_graphs,
+                                   distances=(args.distances or None) if store_graphs is not None else None)
         if args.attention == "edges" and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
             b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
-        if args.distances:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
+        if args.distances and b.pairs is None:   # the batch's pair types: the graphs' cached blocks, concatenated and copied
             b.pairs = PairTypes.from_store(store, hb.graph_ids, b.N, device, args.distances)
         # one sample draw per batch of the stream, in stream order (the sampler is replicated on every rank)
         draws = [model.ss.draw_samples() for _ in range(run.world)]

@@ -33,6 +33,7 @@ EPI_STORE, EPI_BIAS, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU_DROP, EPI_RELU_DROP_BWD,
 ABI_VERSION = 19   # include/u2gnn_hip.h U2GNN_ABI_VERSION
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4
 BIAS_TYPES_MAX = 32   # U2GNN_BIAS_TYPES_MAX: entry types (hop distances) of an attention bias table
+DIST_NODES_MAX = 4096   # U2GNN_DIST_NODES_MAX: the largest graph whose distances the device computes
 
 
 class GemmArgs(ctypes.Structure):
@@ -209,6 +210,11 @@ _HIP_SIGS = {
     "u2gnn_bias_table_grad": ([VP, I64, I32, I32, VP, I64, VP, VP, I64, VP], c_int32),
     "u2gnn_adjacency_assemble": ([POINTER(GraphStructure), VP, VP, VP, I32, I64, I64, VP, VP, VP, VP, VP, VP, VP, VP],
                                  c_int32),
+    "u2gnn_pair_distances": ([POINTER(GraphStructure), VP, VP, VP, I32, I64, I64, I32, I32, VP, VP, VP], c_int32),
+    "u2gnn_pair_distances_u8": ([POINTER(GraphStructure), VP, VP, VP, I32, I64, I64, I32, I32, VP, VP, VP], c_int32),
+    "u2gnn_distance_extents": ([VP, VP, VP, I32, I64, I64, I32, I32, VP, VP, VP, VP], c_int32),
+    "u2gnn_hop_expand_count": ([VP, VP, VP, I32, I64, I64, I32, I32, VP, VP, VP, VP], c_int32),
+    "u2gnn_hop_expand_fill": ([VP, VP, VP, VP, I32, I64, I64, I32, I32, VP, VP, I64, VP, VP, VP, VP, VP, VP], c_int32),
     "u2gnn_layer_fwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, VP, I64, VP, I64,
                               VP, I32, POINTER(CsrAttn), VP, VP], c_int32),
     "u2gnn_layer_bwd_csrb": ([POINTER(LayerDims), POINTER(LayerParamsC), POINTER(LayerSeeds), VP, VP, I64, VP, VP,

@@ -51,17 +51,25 @@ def check_world(run_world: int, flag: int) -> None:
         raise SystemExit(f"WORLD_SIZE={run_world} but --world_size {flag}")
 
 
-def device_graphs(store, device, hops, choice: str, log=print, max_bytes: int = 8 << 30):
-    """--adjacency of the CLIs (with --attention edges): ``device`` = the store's pattern.DeviceGraphs, built once, from
-    which every batch's adjacency is assembled on the GPU; ``host`` = None, and the caller builds each batch's with
-    Adjacency.from_store.  A structure that cannot be kept (larger than max_bytes) logs one line and gives None."""
+def device_graphs(store, device, hops, choice: str, log=print, max_bytes: int = 8 << 30, distances=0):
+    """--adjacency of the CLIs: ``device`` = the store's pattern.DeviceGraphs, built once (with --hops the H-hop lists
+    are expanded on the GPU, build="device"), from which every batch's adjacency is assembled on the GPU (--attention
+    edges) -- or, with ``distances`` (--attention graphs --distances H), the one-hop structure and its extents, from
+    which every batch's pair types are searched on the GPU; ``host`` = None, and the caller builds each batch's with
+    Adjacency.from_store / PairTypes.from_store.  A structure the device route cannot serve (larger than max_bytes, a
+    graph above the search's node bound or scratch) logs one line and gives None."""
     if choice != "device":
         return None
     from .pattern import DeviceGraphs
     try:
-        return DeviceGraphs.from_store(store, device, hops=hops or None, max_bytes=max_bytes)
+        if distances:
+            DeviceGraphs._chunks(store.n_nodes, 1, 256 << 20)       # a graph the device does not search: ValueError
+            dg = DeviceGraphs.from_store(store, device, max_bytes=max_bytes)
+            dg.extents()
+            return dg
+        return DeviceGraphs.from_store(store, device, hops=hops or None, max_bytes=max_bytes, build="device")
     except ValueError as e:
-        log(f"--adjacency device: {e}; building each batch's adjacency on the host")
+        log(f"--adjacency device: {e}; building each batch's {'pair types' if distances else 'adjacency'} on the host")
         return None
 
 

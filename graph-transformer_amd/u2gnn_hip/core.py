@@ -75,8 +75,9 @@ class DeviceBatch:
     # the rows' attention pattern (attention="edges"): Adjacency.from_csr(*store.adjacency(graph_ids), N, device), or
     # the same arrays assembled on the GPU (from_store(..., graphs=DeviceGraphs)); the other modes never read it
     adj: Optional[Adjacency] = None
-    # the pair types of attention="graphs" with ``distances``: PairTypes.from_store(store, graph_ids, N, device, H);
-    # the other modes never read it
+    # the pair types of attention="graphs" with ``distances``: PairTypes.from_store(store, graph_ids, N, device, H), or
+    # the same integers searched on the GPU (from_store(..., graphs=DeviceGraphs, distances=H)); the other modes never
+    # read it
     pairs: Optional[PairTypes] = None
 
     def __post_init__(self):
@@ -110,7 +111,7 @@ class DeviceBatch:
                            rows_contiguous=True)
 
     @staticmethod
-    def from_store(hb, X_dev: torch.Tensor, device="cuda", graphs=None):
+    def from_store(hb, X_dev: torch.Tensor, device="cuda", graphs=None, distances=None):
         """A natively assembled batch (GraphStore.assemble(..., gather_x=False)) -> HBM: input_x, offsets
         and the rows' dataset node ids cross PCIe asynchronously from page-locked buffers (~0.7 MB at
         C4 instead of the 7 MB X_concat; BatchLoader assembles straight into a ring of them);
@@ -118,17 +119,24 @@ class DeviceBatch:
         (u2gnn_gather_rows).  No host synchronisation.
         graphs: the store's pattern.DeviceGraphs -- the batch also gets its adjacency (``adj``, attention="edges"),
         assembled on the GPU from the device-resident structure: the graph ids and entry offsets travel with the
-        arrays above, the row offsets are the batch's own, and the kernel runs beside the feature gather."""
+        arrays above, the row offsets are the batch's own, and the kernel runs beside the feature gather.
+        distances = H (with ``graphs`` a structure built without hops): the batch gets its pair types instead (``pairs``,
+        attention="graphs" with distances=H, no ``adj``), searched on the GPU from the one-hop structure
+        (DeviceGraphs.launch_pairs) in the same place: ids and pair offsets travel with the arrays above."""
         from . import kernels as K
+        if distances and graphs is None:
+            raise ValueError("distances: the pair types are searched from graphs=DeviceGraphs (built without hops)")
         dev = torch.device(device)
         N, B = int(hb.offsets[-1]), len(hb.offsets) - 1
         slot = getattr(hb, "pinned", None)
         _check_range_host(hb.input_x, N)
         plan = None
-        if graphs is not None:   # host tables only: the ids checked, the entry offsets, nnz and n_types
-            plan = graphs.plan(hb.graph_ids)
+        if graphs is not None:   # host tables only: the ids checked, the entry (pair) offsets, nnz (pairs) and n_types
+            plan = graphs.plan_pairs(hb.graph_ids, distances) if distances else graphs.plan(hb.graph_ids)
             if plan[3] != N or len(plan[0]) != B:
                 raise ValueError(f"graphs: the structure gives the batch {plan[3]} rows, the batch has {N}")
+            if distances:
+                n_types = graphs.n_pair_types(plan[0], distances)
         if slot is not None and dev.type == "cuda":
             # the batch's transfers and its feature gather run on a copy stream, so the next batch
             # crosses PCIe while the current step computes; the compute stream waits on one event
@@ -149,19 +157,25 @@ class DeviceBatch:
                 if N:
                     K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
                 err = torch.zeros(1, device=dev, dtype=torch.int32)
-                adj = None if plan is None else graphs.launch(gid, off, ent_off, *plan[3:])
+                adj = pairs = None
+                if distances:
+                    pairs = graphs.launch_pairs(gid, off, ent_off, *plan[3:], distances, n_types)
+                elif plan is not None:
+                    adj = graphs.launch(gid, off, ent_off, *plan[3:])
             ready = torch.cuda.Event()
             ready.record(cs)
             main.wait_event(ready)
             used = [ix, gnode, off, lab, X, err]   # allocated on the copy stream, used on the compute one
             if adj is not None:   # (the adjacency's five arrays are views of one buffer, rowptr its start)
                 used += [gid, ent_off, adj.rowptr] + ([adj.etype] if adj.etype is not None else [])
+            if pairs is not None:   # (pair_off is ent_off)
+                used += [gid, ent_off, pairs.etype]
             for t in used:
                 t.record_stream(main)
             iy = gnode if hb.input_y is not None else None
             colidx, vals = _pool_iota(N, dev)
             return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True, rows_contiguous=True,
-                               adj=adj)
+                               adj=adj, pairs=pairs)
         if slot is not None:
             k1 = hb.input_x.shape[1]
             h2d = lambda t: t.to(dev, non_blocking=True)  # noqa: E731
@@ -180,8 +194,13 @@ class DeviceBatch:
         if N:
             K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
         colidx, vals = _pool_iota(N, dev)
-        adj = None if graphs is None else graphs.adjacency(hb.graph_ids, off)
-        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True, adj=adj)
+        adj = pairs = None
+        if distances:
+            pairs = graphs.pair_types(hb.graph_ids, distances, off)
+        elif graphs is not None:
+            adj = graphs.adjacency(hb.graph_ids, off)
+        return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True, adj=adj,
+                           pairs=pairs)
 
     @staticmethod
     def from_reference_inputs(input_x, graph_pool, X_concat, labels=None):

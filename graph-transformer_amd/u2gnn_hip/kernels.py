@@ -455,6 +455,79 @@ def adjacency_assemble(structure, gid, row_off, ent_off, N, nnz, rowptr, colidx,
                                              _p(etype), _p(err), _s()), "u2gnn_adjacency_assemble")
 
 
+def _slots(gid, row_off, pair_off, err, who):
+    """The slot arrays every distance kernel takes: (B,) after the checks of type and length."""
+    idx = tuple(t for t in (gid, row_off, pair_off) if t is not None)
+    _dev(*idx, err)
+    B = row_off.numel() - 1
+    if any(t.dtype != torch.int64 or not t.is_contiguous() for t in idx) or err.dtype != torch.int32 or err.numel() < 1:
+        raise _lib.U2GNNNativeError(f"{who}: contiguous int64 slot arrays and an int32 err")
+    if B < 1 or pair_off.numel() != B + 1 or (gid is not None and gid.numel() != B):
+        raise _lib.U2GNNNativeError(f"{who}: one graph id per slot, row_off and pair_off one value more")
+    return B
+
+
+def pair_distances(structure, gid, row_off, pair_off, N, n_pairs, max_nodes, H, out, err):
+    """A batch's clipped shortest-path distances from the one-hop structure (structure: _lib.GraphStructure of a
+    pattern.DeviceGraphs built without hops): gid int64 [B], row_off / pair_off int64 [B+1] on the device; out receives
+    out[pair_off[b] + i n + j] = min(dist(i -> j), H) for the n nodes of slot b -- int32 (H in [1, 31]: a batch's pair
+    types) or uint8 (any cap H in [1, 32]: the dense blocks of the expansion), at least n_pairs values.  max_nodes: the
+    largest graph of the batch (above U2GNN_DIST_NODES_MAX the entry point refuses).  err int32 [1] is set to 1 when a
+    slot or an index is out of range (such rows are written as 0).  One launch on the current stream."""
+    B = _slots(gid, row_off, pair_off, err, "pair_distances")
+    _dev(out)
+    if out.dtype not in (torch.int32, torch.uint8) or not out.is_contiguous() or out.numel() < n_pairs:
+        raise _lib.U2GNNNativeError("pair_distances: a contiguous int32 or uint8 output of at least n_pairs values")
+    name = "u2gnn_pair_distances" if out.dtype == torch.int32 else "u2gnn_pair_distances_u8"
+    check(getattr(hip_lib(), name)(ctypes.byref(structure), _p(gid), _p(row_off), _p(pair_off), int(B), int(N),
+                                   int(n_pairs), int(max_nodes), int(H), _p(out), _p(err), _s()), name)
+
+
+def distance_extents(D, row_off, pair_off, N, n_pairs, max_nodes, cap, ecc, fin, err):
+    """Per slot of the dense blocks D (uint8, cap ``cap``): ecc[b] = max min(D, cap - 1), fin[b] = the largest D below
+    cap; ecc, fin int32 [B]."""
+    B = _slots(None, row_off, pair_off, err, "distance_extents")
+    _dev(D, ecc, fin)
+    if D.dtype != torch.uint8 or not D.is_contiguous() or D.numel() < n_pairs or any(
+            t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < B for t in (ecc, fin)):
+        raise _lib.U2GNNNativeError("distance_extents: uint8 D of n_pairs values, int32 ecc and fin of B")
+    check(hip_lib().u2gnn_distance_extents(_p(D), _p(row_off), _p(pair_off), int(B), int(N), int(n_pairs),
+                                           int(max_nodes), int(cap), _p(ecc), _p(fin), _p(err), _s()),
+          "u2gnn_distance_extents")
+
+
+def hop_expand_count(D, row_off, pair_off, N, n_pairs, max_nodes, H, cnt, t_cnt, err):
+    """From the dense blocks D (uint8, cap H + 1) of a chunk: cnt[r] / t_cnt[r] (int64, at least N) = the pairs within
+    H in row / column r of the chunk."""
+    _slots(None, row_off, pair_off, err, "hop_expand_count")
+    _dev(D, cnt, t_cnt)
+    if D.dtype != torch.uint8 or not D.is_contiguous() or D.numel() < n_pairs or any(
+            t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < N for t in (cnt, t_cnt)):
+        raise _lib.U2GNNNativeError("hop_expand_count: uint8 D of n_pairs values, int64 counts of N")
+    check(hip_lib().u2gnn_hop_expand_count(_p(D), _p(row_off), _p(pair_off), row_off.numel() - 1, int(N), int(n_pairs),
+                                           int(max_nodes), int(H), _p(cnt), _p(t_cnt), _p(err), _s()),
+          "u2gnn_hop_expand_count")
+
+
+def hop_expand_fill(D, L, row_off, pair_off, N, n_pairs, max_nodes, H, rowptr, t_rowptr, col, etype, t_src, t_eid, err):
+    """The chunk's part of an H-hop structure from its dense blocks: rowptr / t_rowptr (int64, the chunk's N values of
+    the dataset-wide row pointers), col / t_src / t_eid (int32 [E]) and etype (uint8 [E]) the whole dataset's arrays; L
+    (int16 storage, n_pairs values) is scratch."""
+    _slots(None, row_off, pair_off, err, "hop_expand_fill")
+    _dev(D, L, rowptr, t_rowptr, col, etype, t_src, t_eid)
+    E = col.numel()
+    ok = (D.dtype == torch.uint8 and etype.dtype == torch.uint8 and L.dtype == torch.int16 and D.numel() >= n_pairs
+          and L.numel() >= n_pairs and all(t.dtype == torch.int64 and t.numel() >= N for t in (rowptr, t_rowptr))
+          and all(t.dtype == torch.int32 and t.numel() == E for t in (col, t_src, t_eid)) and etype.numel() == E
+          and all(t.is_contiguous() for t in (D, L, rowptr, t_rowptr, col, etype, t_src, t_eid)))
+    if not ok:
+        raise _lib.U2GNNNativeError("hop_expand_fill: uint8 D, int16 L, int64 row pointers of N, E-entry outputs")
+    check(hip_lib().u2gnn_hop_expand_fill(_p(D), _p(L), _p(row_off), _p(pair_off), row_off.numel() - 1, int(N),
+                                          int(n_pairs), int(max_nodes), int(H), _p(rowptr), _p(t_rowptr), int(E),
+                                          _p(col), _p(etype), _p(t_src), _p(t_eid), _p(err), _s()),
+          "u2gnn_hop_expand_fill")
+
+
 def rowdot(A, lda, B, ldb, out, rows, cols):
     _dev(A, B, out)
     check(hip_lib().u2gnn_rowdot(_p(A), int(lda), _p(B), int(ldb), _p(out), int(rows), int(cols), _s()),

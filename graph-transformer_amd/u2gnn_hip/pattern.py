@@ -1,7 +1,13 @@
 """Which rows a row attends over, said once: the model's ``attention`` / ``hops`` / ``distances`` keywords
 (check_attention, check_hops, check_distances), the batch's device-resident adjacency (Adjacency) or pair types
 (PairTypes) and the value every layer call takes (AttnPattern), which alone turns a pattern into the arguments of the
-C ABI (u2gnn_layer_*_csrb, u2gnn_layer_*_segb, u2gnn_csr_attn_*)."""
+C ABI (u2gnn_layer_*_csrb, u2gnn_layer_*_segb, u2gnn_csr_attn_*).
+
+Where ``adj`` and ``pairs`` come from: the host builds them per batch from the store (Adjacency.from_store,
+PairTypes.from_store), or the GPU does from a dataset's DeviceGraphs -- ``adjacency(ids)`` assembles a batch's adjacency
+from the resident pieces (which ``from_store(..., hops=H, build="device")`` expands on the GPU from the one-hop lists),
+``pair_types(ids, H)`` searches a batch's shortest-path distances from the one-hop structure.  Both routes give the
+same integers."""
 from __future__ import annotations
 
 import ctypes
@@ -10,7 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import BIAS_TYPES_MAX, U2GNNNativeError
+from ._lib import BIAS_TYPES_MAX, DIST_NODES_MAX, U2GNNNativeError
 
 ATTENTION_MODES = ("nodes", "neighbors", "graphs", "edges")
 BIAS_ENTRIES_MAX = 4096 * 112 * 256   # the entries u2gnn_bias_table_grad reduces in one call (u2gnn_hip.h)
@@ -192,26 +198,49 @@ class DeviceGraphs:
 
     The host keeps each graph's node count, entry count and largest distance: a batch's N, nnz and n_types come from
     them, never from the device.  ``adjacency(ids)`` equals ``Adjacency.from_csr(*store.adjacency(ids, hops), N,
-    device)`` integer for integer; ``assemble_numpy(ids)`` is the numpy statement of the same assembly."""
+    device)`` integer for integer; ``assemble_numpy(ids)`` is the numpy statement of the same assembly.
+
+    A structure built without ``hops`` is also where the shortest-path search starts (csrc/distances.hip; graphs of up
+    to DIST_NODES_MAX nodes): ``pair_types(ids, H)`` equals ``PairTypes.from_store(store, ids, N, device, H)``, and
+    ``expand(H)`` -- what ``from_store(..., hops=H, build="device")`` returns -- equals the host-built H-hop structure;
+    ``pair_types_numpy`` and ``expand_numpy`` are their numpy statements."""
     ARRAYS = ("node_start", "ent_start", "rowptr", "t_rowptr", "col", "t_src", "t_eid", "etype")
 
-    def __init__(self, host: dict, hops, device):
+    def __init__(self, host, hops, device, dev=None, tables=None):
+        """host: the numpy arrays (etype None without hops).  A structure expanded on the device (``expand``) comes
+        with its device arrays ``dev`` and the host tables (n_nodes, n_entries, max_dist) instead, host None: the
+        arrays are copied back on first use of ``host``."""
         self.hops, self.device = hops, torch.device(device)
-        self.host = host                                           # the numpy arrays (etype None without hops)
-        self.G, self.V, self.E = len(host["node_start"]) - 1, int(host["node_start"][-1]), int(host["ent_start"][-1])
-        self.n_nodes = np.diff(host["node_start"])
-        self.n_entries = np.diff(host["ent_start"])
-        et = host["etype"]
-        if et is None or not self.E:
-            self.max_dist = np.zeros(self.G, dtype=np.int64)
-        else:   # per graph; a graph without entries (no nodes) keeps 0
-            self.max_dist = np.maximum.reduceat(et, np.minimum(host["ent_start"][:-1], self.E - 1)).astype(np.int64)
-            self.max_dist[self.n_entries == 0] = 0
-        self.dev = {k: None if host[k] is None else torch.from_numpy(host[k]).to(self.device) for k in self.ARRAYS}
+        self._host = host
+        if dev is None:
+            self.n_nodes = np.diff(host["node_start"])
+            self.n_entries = np.diff(host["ent_start"])
+            self.E = int(host["ent_start"][-1])
+            et = host["etype"]
+            if et is None or not self.E:
+                self.max_dist = np.zeros(len(self.n_nodes), dtype=np.int64)
+            else:   # per graph; a graph without entries (no nodes) keeps 0
+                self.max_dist = np.maximum.reduceat(et, np.minimum(host["ent_start"][:-1], self.E - 1)).astype(np.int64)
+                self.max_dist[self.n_entries == 0] = 0
+            self.dev = {k: None if host[k] is None else torch.from_numpy(host[k]).to(self.device) for k in self.ARRAYS}
+        else:
+            self.n_nodes, self.n_entries, self.max_dist = tables
+            self.E = int(self.n_entries.sum())
+            self.dev = dev
+        self.G, self.V = len(self.n_nodes), int(self.n_nodes.sum())
         self.err = torch.zeros(1, device=self.device, dtype=torch.int32)   # set by the kernel, never on checked ids
         if self.device.type == "cuda":   # built once; batches are assembled on other streams (DeviceBatch.from_store)
             torch.cuda.current_stream(self.device).synchronize()
         self._c = None
+        self._extents = None
+        self.last_expand = None                                    # (chunks, scratch bytes) of ``expand``
+
+    @property
+    def host(self) -> dict:
+        """The numpy arrays; of a structure expanded on the device, copied back on first use."""
+        if self._host is None:
+            self._host = {k: None if self.dev[k] is None else self.dev[k].cpu().numpy() for k in self.ARRAYS}
+        return self._host
 
     @staticmethod
     def nbytes(G: int, V: int, E: int, hops) -> int:
@@ -219,14 +248,27 @@ class DeviceGraphs:
         return 16 * (G + 1) + 16 * (V + 1) + (13 if hops else 12) * E
 
     @staticmethod
-    def from_store(store, device="cuda", hops=None, max_bytes=8 << 30) -> "DeviceGraphs":
+    def from_store(store, device="cuda", hops=None, max_bytes=8 << 30, build="host",
+                   scratch_bytes=256 << 20) -> "DeviceGraphs":
         """The structure of all of ``store``'s graphs (any store with ``n_nodes`` and ``adjacency(ids, hops=)``), built
         once on the host from one ``store.adjacency(range(G), hops)`` and its transpose (as ``Adjacency.from_csr``
         takes it), rewritten into each graph's own numbering, then moved to ``device``.  hops None or 0: off.
         ValueError: ``hops`` outside [1, 31]; a graph with 2^31 or more nodes or entries; arrays larger than
-        ``max_bytes`` (known from the counts, before anything is allocated on or copied to the device)."""
+        ``max_bytes`` (known from the counts, before anything is allocated on or copied to the device).
+
+        build="device" with ``hops`` on a GPU: only the one-hop structure is built on the host; the shortest-path
+        search and the H-hop lists are the GPU's (``expand``), in chunks of graphs whose dense scratch fits
+        ``scratch_bytes``.  The arrays, ``n_entries`` and ``max_dist`` equal the host build's integer for integer.
+        ValueError also for a graph above DIST_NODES_MAX nodes or one whose scratch exceeds ``scratch_bytes``.  A CPU
+        device, or no ``hops``, builds on the host whatever ``build`` says."""
         from .batching import check_hops_range
         hops = check_hops_range(hops) if hops else None
+        if build not in ("host", "device"):
+            raise ValueError(f"device graphs: build must be 'host' or 'device', got {build!r}")
+        if build == "device" and hops and torch.device(device).type == "cuda":
+            DeviceGraphs._chunks(np.asarray(store.n_nodes, dtype=np.int64), DeviceGraphs.EXPAND_BYTES, scratch_bytes)
+            one = DeviceGraphs.from_store(store, device, None, max_bytes)
+            return one.expand(hops, scratch_bytes, max_bytes)
         n = np.asarray(store.n_nodes, dtype=np.int64)
         G, V = len(n), int(n.sum())
         if G < 1 or V < 1:
@@ -343,6 +385,235 @@ class DeviceGraphs:
         """IndexError if a launch met a slot or an index out of range (host sync)."""
         if int(self.err.item()):
             raise IndexError("device graphs: a graph id or an index out of range reached the kernel")
+
+    # ---- shortest-path distances from the one-hop structure (u2gnn_pair_distances, u2gnn_hop_expand_*) ----
+    EXPAND_BYTES = 3      # dense scratch per pair of the expansion: the distance (uint8) and the pair's rank (uint16)
+
+    def _one_hop(self, what):
+        if self.hops:
+            raise ValueError(f"device graphs: {what} starts from a structure built without hops")
+
+    @staticmethod
+    def _chunks(n_nodes, per_pair: int, scratch_bytes: int):
+        """The graph ranges [g0, g1) the dataset is searched in: consecutive graphs whose dense blocks (``per_pair``
+        bytes for each of a graph's n^2 pairs) fit ``scratch_bytes`` together.  ValueError for a graph above
+        DIST_NODES_MAX nodes or one that alone needs more than ``scratch_bytes``."""
+        n = np.asarray(n_nodes, dtype=np.int64)
+        if len(n) and int(n.max()) > DIST_NODES_MAX:
+            raise ValueError(f"device graphs: a graph of {int(n.max())} nodes, the device searches at most "
+                             f"{DIST_NODES_MAX} (the host path serves it)")
+        need = per_pair * n * n
+        if len(n) and int(need.max()) > scratch_bytes:
+            raise ValueError(f"device graphs: one graph needs {int(need.max())} bytes of scratch, more than "
+                             f"scratch_bytes = {scratch_bytes}")
+        ends = np.cumsum(need)
+        out, g0 = [], 0
+        while g0 < len(n):
+            g1 = int(np.searchsorted(ends, (ends[g0 - 1] if g0 else 0) + scratch_bytes, side="right"))
+            out.append((g0, g1))
+            g0 = g1
+        return out
+
+    def _chunk_slots(self, g0: int, g1: int, n_nodes=None):
+        """(gid, row_off, pair_off) on the device, N, n_pairs, max_nodes of the chunk of graphs [g0, g1): sent from
+        page-locked memory without blocking.  n_nodes: the node counts to plan with (a graph counted as 0 is left
+        out of the chunk)."""
+        C = g1 - g0
+        n = (self.n_nodes if n_nodes is None else n_nodes)[g0:g1]
+        stage = torch.empty(3 * C + 2, dtype=torch.int64, pin_memory=self.device.type == "cuda")
+        h = stage.numpy()
+        h[:C] = np.arange(g0, g1)
+        h[C], h[2 * C + 1] = 0, 0
+        np.cumsum(n, out=h[C + 1:2 * C + 1])
+        np.cumsum(n * n, out=h[2 * C + 2:])
+        N, n_pairs = int(h[2 * C]), int(h[3 * C + 1])
+        d = stage.to(self.device, non_blocking=True)
+        return (d[:C], d[C:2 * C + 1], d[2 * C + 1:]), N, n_pairs, int(n.max())
+
+    def extents(self, scratch_bytes=256 << 20):
+        """(ecc31, fin31), int64 [G] on the host: per graph the largest min(distance, 31) over all pairs, an unreachable
+        pair counting as 31, and the same over the reachable pairs only.  Computed once on the device at cap 32, in
+        chunks whose dense blocks fit ``scratch_bytes``, and kept: a batch's ``n_types`` is max min(ecc31, H) + 1 and
+        an H-hop structure's ``max_dist`` is min(fin31, H), without reading the device again.  A graph the device does
+        not search (above DIST_NODES_MAX nodes) keeps 0: ``pair_types`` refuses it."""
+        from . import kernels as K
+        self._one_hop("extents")
+        if self._extents is None:
+            small = self.n_nodes <= DIST_NODES_MAX
+            n_small = np.where(small, self.n_nodes, 0)
+            ecc = torch.zeros(self.G, device=self.device, dtype=torch.int32)
+            fin = torch.zeros(self.G, device=self.device, dtype=torch.int32)
+            plans = [(g0, g1) + self._chunk_slots(g0, g1, n_small) for g0, g1 in self._chunks(n_small, 1, scratch_bytes)]
+            size = max([p[4] for p in plans] + [1])
+            D = torch.empty(size, device=self.device, dtype=torch.uint8)
+            for g0, g1, (gid, row_off, pair_off), N, n_pairs, max_n in plans:
+                if n_pairs < 1:
+                    continue
+                K.pair_distances(self.c_struct(), gid, row_off, pair_off, N, n_pairs, max_n, BIAS_TYPES_MAX, D, self.err)
+                K.distance_extents(D, row_off, pair_off, N, n_pairs, max_n, BIAS_TYPES_MAX, ecc[g0:g1], fin[g0:g1],
+                                   self.err)
+            self._extents = (ecc.cpu().numpy().astype(np.int64), fin.cpu().numpy().astype(np.int64))
+            self.check_indices()
+        return self._extents
+
+    def plan_pairs(self, graph_ids, H: int):
+        """(ids, row_off, pair_off, N, n_pairs, max_nodes) of the batch's pair types, from the host tables alone.
+        ValueError: H outside [1, 31], an empty batch, an id outside [0, G), a graph above DIST_NODES_MAX nodes, no pair
+        or more than BIAS_ENTRIES_MAX."""
+        from .batching import check_hops_range
+        self._one_hop("pair_types")
+        check_hops_range(H)
+        ids = np.ascontiguousarray(graph_ids, dtype=np.int64).reshape(-1)
+        if ids.shape[0] < 1 or ids.min() < 0 or ids.max() >= self.G:
+            raise ValueError(f"device graphs: a batch of at least one graph id in [0, {self.G})")
+        n = self.n_nodes[ids]
+        if int(n.max()) > DIST_NODES_MAX:
+            raise ValueError(f"device graphs: a graph of {int(n.max())} nodes, the device searches at most "
+                             f"{DIST_NODES_MAX} (the host path serves it)")
+        row_off, pair_off = np.zeros(len(ids) + 1, dtype=np.int64), np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum(n, out=row_off[1:])
+        np.cumsum(n * n, out=pair_off[1:])
+        if not 1 <= int(pair_off[-1]) <= BIAS_ENTRIES_MAX:
+            raise ValueError(f"pair types: between 1 and {BIAS_ENTRIES_MAX} pairs, got {int(pair_off[-1])}")
+        return ids, row_off, pair_off, int(row_off[-1]), int(pair_off[-1]), int(n.max())
+
+    def _dense_numpy(self, g: int, cap: int) -> np.ndarray:
+        """Graph g's [n, n] block min(distance, cap) as the kernel sweeps it: filled with cap, 0 on the diagonal; in
+        sweep h = 1 .. cap - 1 an unset node takes h if one of its in-neighbours (t_src of its transposed list) holds
+        h - 1; stop when a sweep sets nothing."""
+        h_ = self.host
+        n, v0 = int(self.n_nodes[g]), int(h_["node_start"][g])
+        D = np.full((n, n), cap, dtype=np.uint8)
+        D[np.arange(n), np.arange(n)] = 0
+        tr = h_["t_rowptr"][v0:v0 + n + 1]
+        into = np.zeros((n, n), dtype=np.float32)                   # into[s][u] = 1: s is an in-neighbour of u
+        into[h_["t_src"][tr[0]:tr[-1]], np.repeat(np.arange(n), np.diff(tr))] = 1
+        for h in range(1, cap):
+            new = (D == cap) & (((D == h - 1).astype(np.float32) @ into) > 0)
+            if not new.any():
+                break
+            D[new] = h
+        return D
+
+    def pair_types_numpy(self, graph_ids, H: int):
+        """(pair_off int64 [B+1], etype int32 [n_pairs]) of the batch as host numpy arrays: what u2gnn_pair_distances
+        writes, and what ``store.distances(ids, H)`` returns."""
+        ids, _, pair_off, _, n_pairs, _ = self.plan_pairs(graph_ids, H)
+        etype = np.empty(n_pairs, dtype=np.int32)
+        for b, g in enumerate(ids):
+            etype[pair_off[b]:pair_off[b + 1]] = self._dense_numpy(int(g), H).reshape(-1)
+        return pair_off, etype
+
+    def pair_types(self, graph_ids, H: int, row_off_dev=None) -> PairTypes:
+        """The PairTypes of the batch ``graph_ids`` (in that order) with distances clipped at H, searched on the device
+        from this one-hop structure: planned on the host (``plan_pairs``; n_types from ``extents``), ids and offsets
+        leave from page-locked memory without blocking, one launch of u2gnn_pair_distances on the current stream.
+        Equals ``PairTypes.from_store(store, ids, N, device, H)``.  row_off_dev: the batch's row offsets when they
+        are on the device already."""
+        ids, row_off, pair_off, N, n_pairs, max_n = self.plan_pairs(graph_ids, H)
+        B = len(ids)
+        stage = torch.empty(3 * B + 2, dtype=torch.int64, pin_memory=self.device.type == "cuda")
+        h = stage.numpy()
+        h[:B], h[B:2 * B + 1], h[2 * B + 1:] = ids, pair_off, row_off
+        n_send = 2 * B + 1 if row_off_dev is not None else 3 * B + 2
+        d = stage[:n_send].to(self.device, non_blocking=True)
+        return self.launch_pairs(d[:B], d[2 * B + 1:] if row_off_dev is None else row_off_dev, d[B:2 * B + 1], N,
+                                 n_pairs, max_n, H, self.n_pair_types(ids, H))
+
+    def n_pair_types(self, ids, H: int) -> int:
+        """max(etype) + 1 of the batch's pair types, from ``extents`` alone."""
+        return int(np.minimum(self.extents()[0][ids], H).max()) + 1
+
+    def launch_pairs(self, gid, row_off, pair_off, N: int, n_pairs: int, max_nodes: int, H: int, n_types: int) -> PairTypes:
+        """The batch's PairTypes from device int64 ``gid`` [B], ``row_off`` / ``pair_off`` [B+1] (``plan_pairs``'s
+        arrays): allocates etype and launches u2gnn_pair_distances on the current stream."""
+        from . import kernels as K
+        etype = torch.empty(n_pairs, device=gid.device, dtype=torch.int32)
+        K.pair_distances(self.c_struct(), gid, row_off, pair_off, N, n_pairs, max_nodes, H, etype, self.err)
+        return PairTypes(N, pair_off, etype, n_types)
+
+    def expand_numpy(self, H: int) -> dict:
+        """The eight host arrays of the H-hop structure, from the dense blocks of ``_dense_numpy`` (cap H + 1) as the
+        expansion kernels build them: a row keeps the columns with D <= H in ascending order, a column the rows; a
+        transposed entry's id is its row's first entry inside the graph plus the rank of the column in that row."""
+        from .batching import check_hops_range
+        self._one_hop("expand")
+        H = check_hops_range(H)
+        cnt, tcnt, col, et, t_src, t_eid = [], [], [], [], [], []
+        for g in range(self.G):
+            D = self._dense_numpy(g, H + 1)
+            keep = D <= H
+            c = keep.sum(1)
+            first = np.cumsum(c) - c                                # each row's first entry inside the graph
+            rank = np.cumsum(keep, 1) - 1
+            ti, tj = np.nonzero(keep.T)[::-1]                       # grouped by column j, rows i ascending
+            cnt.append(c), tcnt.append(keep.sum(0)), col.append(np.nonzero(keep)[1]), et.append(D[keep])
+            t_src.append(ti), t_eid.append(first[ti] + rank[ti, tj])
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts), dtype=dt)   # noqa: E731
+        rowptr, t_rowptr = np.zeros(self.V + 1, dtype=np.int64), np.zeros(self.V + 1, dtype=np.int64)
+        np.cumsum(cat(cnt, np.int64), out=rowptr[1:])
+        np.cumsum(cat(tcnt, np.int64), out=t_rowptr[1:])
+        node_start = self.host["node_start"]
+        return {"node_start": node_start, "ent_start": np.ascontiguousarray(rowptr[node_start]), "rowptr": rowptr,
+                "t_rowptr": t_rowptr, "col": cat(col, np.int32), "t_src": cat(t_src, np.int32),
+                "t_eid": cat(t_eid, np.int32), "etype": cat(et, np.uint8)}
+
+    def expand(self, H: int, scratch_bytes=256 << 20, max_bytes=8 << 30) -> "DeviceGraphs":
+        """The H-hop structure of the same graphs, expanded on the device from this one-hop structure: per chunk of
+        graphs (``_chunks``) the dense distances at cap H + 1 (u2gnn_pair_distances_u8), the row and column counts and
+        each graph's largest distance; one prefix sum over the dataset's nodes (torch.cumsum) gives rowptr and
+        t_rowptr, the total is read back once and checked against ``max_bytes`` before the entry arrays are
+        allocated; then per chunk the fill (the distances are searched again unless one chunk holds everything).
+        Equals the host build integer for integer; ``last_expand`` keeps (chunks, scratch bytes)."""
+        from . import kernels as K
+        from .batching import check_hops_range
+        self._one_hop("expand")
+        H = check_hops_range(H)
+        if self.device.type != "cuda":
+            raise ValueError("device graphs: expand runs on a GPU")
+        plans = [(g0, g1) + self._chunk_slots(g0, g1)
+                 for g0, g1 in self._chunks(self.n_nodes, self.EXPAND_BYTES, scratch_bytes)]
+        plans = [p for p in plans if p[4] >= 1]
+        ns = self.host["node_start"]
+        size = max(p[4] for p in plans)
+        l_at = size + (-size) % 16                                  # the ranks follow the distances, 16-byte aligned
+        scratch = torch.empty(l_at + 2 * size, device=self.device, dtype=torch.uint8)
+        D, L = scratch[:size], scratch[l_at:].view(torch.int16)
+        dev, i64 = self.device, torch.int64
+        rowptr, t_rowptr = torch.zeros(self.V + 1, device=dev, dtype=i64), torch.zeros(self.V + 1, device=dev, dtype=i64)
+        cnt, t_cnt = torch.empty(self.V, device=dev, dtype=i64), torch.empty(self.V, device=dev, dtype=i64)
+        ecc, fin = (torch.zeros(self.G, device=dev, dtype=torch.int32) for _ in range(2))
+        search = lambda p: K.pair_distances(self.c_struct(), *p[2], p[3], p[4], p[5], H + 1, D, self.err)  # noqa: E731
+        for p in plans:
+            g0, g1, (_, row_off, pair_off), N, n_pairs, max_n = p
+            v0 = int(ns[g0])
+            search(p)
+            K.hop_expand_count(D, row_off, pair_off, N, n_pairs, max_n, H, cnt[v0:v0 + N], t_cnt[v0:v0 + N], self.err)
+            K.distance_extents(D, row_off, pair_off, N, n_pairs, max_n, H + 1, ecc[g0:g1], fin[g0:g1], self.err)
+        torch.cumsum(cnt, 0, out=rowptr[1:])
+        torch.cumsum(t_cnt, 0, out=t_rowptr[1:])
+        del cnt, t_cnt
+        ent_start = rowptr[self.dev["node_start"]].contiguous()
+        n_entries = np.diff(ent_start.cpu().numpy())                # the one read-back of the counts
+        E = int(n_entries.sum())
+        self._check_size(self.G, self.V, E, H, max_bytes)
+        col, t_src, t_eid = (torch.empty(E, device=dev, dtype=torch.int32) for _ in range(3))
+        etype = torch.empty(E, device=dev, dtype=torch.uint8)
+        for p in plans:
+            g0, g1, (_, row_off, pair_off), N, n_pairs, max_n = p
+            v0 = int(ns[g0])
+            if len(plans) > 1:
+                search(p)
+            K.hop_expand_fill(D, L, row_off, pair_off, N, n_pairs, max_n, H, rowptr[v0:v0 + N], t_rowptr[v0:v0 + N],
+                              col, etype, t_src, t_eid, self.err)
+        max_dist = fin.cpu().numpy().astype(np.int64)
+        self.check_indices()
+        out = DeviceGraphs(None, H, dev, dev={"node_start": self.dev["node_start"], "ent_start": ent_start,
+                                              "rowptr": rowptr, "t_rowptr": t_rowptr, "col": col, "t_src": t_src,
+                                              "t_eid": t_eid, "etype": etype},
+                           tables=(self.n_nodes, n_entries, max_dist))
+        out.last_expand = (len(plans), int(scratch.numel()))
+        return out
 
 
 class AttnPattern:

@@ -684,6 +684,54 @@ int u2gnn_adjacency_assemble(const u2gnn_graph_structure *S, const int64_t *gid,
                              int64_t *colidx, int64_t *t_rowptr, int64_t *t_src, int64_t *t_eid, int32_t *etype,
                              int32_t *err, void *stream);
 
+/* ---- shortest-path distances on the device, from the one-hop structure (a u2gnn_graph_structure built without hops:
+ * row v lists v and its out-neighbours, t_rowptr / t_src give v's in-neighbours).  ABI 19 grew by these five entry
+ * points, nothing else changed.  Integers only: every result equals the host builders' (u2gnn_hip.batching.hop_lists,
+ * GraphStore.distances) value for value, and is bit-identical from run to run (no atomics, every output element
+ * written by exactly one thread).
+ * A batch (or a chunk of the dataset) is B slots: gid[b] (device int64 [B]) the graph, row_off / pair_off (device
+ * int64 [B+1]) the slot's first row and first dense element; slot b holds n = row_off[b+1] - row_off[b] nodes and the
+ * n * n elements pair_off[b] .. ; N = row_off[B] rows and n_pairs = pair_off[B] elements in all.  max_nodes: the
+ * largest n of the batch, which the caller knows; the rows are held in LDS, so max_nodes > U2GNN_DIST_NODES_MAX is
+ * U2GNN_E_SHAPE and nothing is launched.
+ * u2gnn_pair_distances: etype[pair_off[b] + i n + j] = min(dist(i -> j), H), H where no path exists, 0 on the diagonal
+ *   (int32 [n_pairs]: the pair types of attention="graphs" with distances=H); H in [1, 31].  One wave per source row,
+ *   level-synchronous pull sweeps over the in-neighbour lists, early exit, the row written coalesced.
+ * u2gnn_pair_distances_u8: the same values as bytes with any cap in [1, 32] (the dense blocks D the expansion reads).
+ * u2gnn_distance_extents: per slot, ecc[b] = max over its pairs of min(D, cap - 1) and fin[b] = the largest D < cap
+ *   (int32 [B] each).
+ * u2gnn_hop_expand_count: from D with cap H + 1, cnt[r] = #{j : D[i][j] <= H} for row r of the chunk and t_cnt[r] =
+ *   #{i : D[i][j] <= H} for the same node as a column (int64 [N] each).  The caller's prefix sums over the dataset's
+ *   nodes give the H-hop structure's rowptr and t_rowptr.
+ * u2gnn_hop_expand_fill: rowptr / t_rowptr: the chunk's N values of those prefix sums (dataset-wide entry indices);
+ *   col, etype, t_src, t_eid: the whole dataset's arrays of E entries, laid out as u2gnn_graph_structure says.  Row
+ *   fill by ordered compaction (64-bit ballot and popcount keep the columns ascending), the rank of each kept pair in
+ *   its row kept in L (uint16, n_pairs elements, scratch); transposed fill per column over ascending rows.
+ * Any content of the device arrays is memory-safe: a slot whose rows, node count or dense block are out of range
+ * writes nothing; a graph id is checked against [0, G), its nodes against [0, V) and the slot's node count, an entry
+ * against [0, E), a t_src value against [0, n), an output position against [0, E) before it is used.  A row that
+ * fails a check is written as type 0; *err (device int32) is set to 1, only ever set, never cleared.
+ * Null pointers, B, N, n_pairs, max_nodes, G, V or E < 1: U2GNN_E_ARG; misaligned arrays: U2GNN_E_ALIGN; H outside
+ * [1, 31], cap outside [1, 32], max_nodes > U2GNN_DIST_NODES_MAX, N >= 2^31: U2GNN_E_SHAPE -- before anything is
+ * launched. */
+#define U2GNN_DIST_NODES_MAX 4096
+int u2gnn_pair_distances(const u2gnn_graph_structure *S, const int64_t *gid, const int64_t *row_off,
+                         const int64_t *pair_off, int32_t B, int64_t N, int64_t n_pairs, int32_t max_nodes, int32_t H,
+                         int32_t *etype, int32_t *err, void *stream);
+int u2gnn_pair_distances_u8(const u2gnn_graph_structure *S, const int64_t *gid, const int64_t *row_off,
+                            const int64_t *pair_off, int32_t B, int64_t N, int64_t n_pairs, int32_t max_nodes,
+                            int32_t cap, uint8_t *D, int32_t *err, void *stream);
+int u2gnn_distance_extents(const uint8_t *D, const int64_t *row_off, const int64_t *pair_off, int32_t B, int64_t N,
+                           int64_t n_pairs, int32_t max_nodes, int32_t cap, int32_t *ecc, int32_t *fin, int32_t *err,
+                           void *stream);
+int u2gnn_hop_expand_count(const uint8_t *D, const int64_t *row_off, const int64_t *pair_off, int32_t B, int64_t N,
+                           int64_t n_pairs, int32_t max_nodes, int32_t H, int64_t *cnt, int64_t *t_cnt, int32_t *err,
+                           void *stream);
+int u2gnn_hop_expand_fill(const uint8_t *D, uint16_t *L, const int64_t *row_off, const int64_t *pair_off, int32_t B,
+                          int64_t N, int64_t n_pairs, int32_t max_nodes, int32_t H, const int64_t *rowptr,
+                          const int64_t *t_rowptr, int64_t E, int32_t *col, uint8_t *etype, int32_t *t_src,
+                          int32_t *t_eid, int32_t *err, void *stream);
+
 /* ---- a3: one encoder layer (TransformerEncoderLayer(d, nhead=1, ff, dropout), post-LN, slot-0
  * rows) issued natively: forward and backward of pytorch_U2GNN_Sup.py:19-21,35 /
  * pytorch_U2GNN_UnSup.py:37-40,57, launch-for-launch the sequence of u2gnn_hip/engine.py.

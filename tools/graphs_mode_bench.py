@@ -17,8 +17,15 @@ per setting (c4: the same synthetic graphs as a GraphStore; mutag: MUTAG from da
   * the host cost of PairTypes.from_store per batch with cached blocks (host clock to the return of the call, and to a
     device synchronise after it).
 
+With --distances H --pipeline it times distances steps on FRESH batches instead (``pair_pipeline``): the pair types
+resident, built on the host per batch (PairTypes.from_store) or searched on the GPU per batch (DeviceGraphs.pair_types
+through DeviceBatch.from_store), and u2gnn_pair_distances alone.  With --build it gives the wall time of
+DeviceGraphs.from_store(hops=H) built on the host against build="device" (``structure_builds``).
+
 Prints one JSON line.  Usage: python tools/graphs_mode_bench.py [--steps 24] [--warmup 5] [--batches 4]
-       python tools/graphs_mode_bench.py --distances 3 [--settings c4,mutag] [--csr_hops 2]"""
+       python tools/graphs_mode_bench.py --distances 3 [--settings c4,mutag] [--csr_hops 2]
+       python tools/graphs_mode_bench.py --distances 3 --pipeline [--steps 32] [--settings c4,mutag]
+       python tools/graphs_mode_bench.py --build c4:2,c4:3,ptc:3,ptc:31"""
 import argparse
 import json
 import math
@@ -203,18 +210,147 @@ def distance_setting(name, store, C, batch_size, k, args):
                         for h, b in list(zip(host, batches))[:2]]}
 
 
+def pair_pipeline(name, store, C, batch_size, k, args):
+    """attention="graphs" with distances=H steps on FRESH batches from a BatchLoader over a GraphStore, three variants
+    in rotating blocks of one process, one trainer:
+
+      resident: --batches batches built up front and replayed;
+      host:     every step draws a batch and builds its pair types on the host (PairTypes.from_store, blocks cached
+                after the warm-up passes) -- the CLIs' --adjacency host;
+      device:   every step draws a batch and DeviceBatch.from_store(..., graphs=, distances=H) searches its pair types
+                on the GPU -- the CLIs' --adjacency device.
+
+    A block is --block steps between two synchronisations, timed on the host clock; per variant the median of its
+    blocks' per-step times.  pass: device no slower than host by more than the spread (max - min) of host's own
+    blocks.  The one-hop structure's build and its extents are timed apart; u2gnn_pair_distances alone is timed as
+    REPS launches in one HIP graph."""
+    import time
+    from pytorch_U2GNN_Sup import TransformerU2GNN
+    from u2gnn_hip.batching import BatchLoader
+    from u2gnn_hip.core import DeviceBatch, PairTypes
+    from u2gnn_hip.pattern import DeviceGraphs
+    from u2gnn_hip.train import SupTrainer
+    T, ff, H = 4, 1024, args.distances
+    t0 = time.perf_counter()
+    dg = DeviceGraphs.from_store(store, "cuda")
+    build_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    dg.extents()
+    extents_s = time.perf_counter() - t0
+    X_dev = torch.from_numpy(store.X).cuda()
+    np.random.seed(123)
+    loader = BatchLoader(store, batch_size, k, gather_x=False)
+    resident = [DeviceBatch.from_store(loader(), X_dev, "cuda", graphs=dg, distances=H) for _ in range(args.batches)]
+    torch.manual_seed(123)
+    m = TransformerU2GNN(store.d, ff, C, T, 0.5, 1, precision=args.precision, attention="graphs", distances=H)
+    tr = SupTrainer(m.cuda().train(), lr=5e-4, max_norm=0.5, seed=123)
+    count = [0]
+
+    def feed_resident():
+        count[0] += 1
+        return resident[count[0] % len(resident)]
+
+    def feed_host():
+        hb = loader()
+        b = DeviceBatch.from_store(hb, X_dev, "cuda")
+        b.pairs = PairTypes.from_store(store, hb.graph_ids, b.N, "cuda", H)
+        return b
+
+    def feed_device():
+        return DeviceBatch.from_store(loader(), X_dev, "cuda", graphs=dg, distances=H)
+    feeds = {"resident": feed_resident, "host": feed_host, "device": feed_device}
+    names = tuple(feeds)
+    t0 = time.perf_counter()
+    store.distances(np.arange(dg.G), H)                        # the host path's blocks, all cached before the timing
+    host_cache_s = time.perf_counter() - t0
+    for f in feeds.values():
+        for _ in range(args.warmup):
+            tr.step(f())
+    torch.cuda.synchronize()
+    blocks = {n: [] for n in names}
+    done, blk = 0, 0
+    while done < args.steps:
+        r = blk % len(names)
+        n = min(args.block, args.steps - done)
+        for v in names[r:] + names[:r]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tr.step(feeds[v]())
+            torch.cuda.synchronize()
+            blocks[v].append((time.perf_counter() - t0) * 1e3 / n)
+        done += n
+        blk += 1
+    med = {v: statistics.median(t) for v, t in blocks.items()}
+    spread = max(blocks["host"]) - min(blocks["host"])
+    dg.check_indices()
+    ids, row_off, pair_off, N, n_pairs, max_n = dg.plan_pairs(loader.rng.permutation(dg.G)[:batch_size], H)
+    to = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    gid, ro, po = to(ids), to(row_off), to(pair_off)
+    et = torch.empty(n_pairs, device="cuda", dtype=torch.int32)
+    us = graph_time_us(lambda: K.pair_distances(dg.c_struct(), gid, ro, po, N, n_pairs, max_n, H, et, dg.err))
+    return {"setting": f"{name}: bs {batch_size}, k {k}, d {store.d}, T {T}, ff {ff}, {args.precision}, distances {H}, "
+                       f"fresh batches, {args.steps} steps per variant in rotating blocks of {args.block}, host clock",
+            "structure": {"graphs": dg.G, "nodes": dg.V, "entries": dg.E, "one_hop_build_s": round(build_s, 3),
+                          "extents_s": round(extents_s, 3), "host_blocks_all_graphs_s": round(host_cache_s, 3)},
+            "step_ms": {v: round(t, 4) for v, t in med.items()},
+            "block_ms_min_max": {v: [round(min(t), 4), round(max(t), 4)] for v, t in blocks.items()},
+            "device_over_resident": round(med["device"] / med["resident"], 4),
+            "host_over_resident": round(med["host"] / med["resident"], 4),
+            "host_block_spread_ms": round(spread, 4),
+            "pass": bool(med["device"] <= med["host"] + spread),
+            "pair_distances": {"rows": N, "pairs": n_pairs, "max_nodes": max_n, "us": round(us, 2)}}
+
+
+def structure_builds(args):
+    """The wall time of DeviceGraphs.from_store(hops=H), built on the host and with build="device", one run each in
+    this process after a warm-up build of MUTAG; the results compared integer for integer."""
+    import time
+    import util
+    from u2gnn_hip.batching import GraphStore
+    from u2gnn_hip.pattern import DeviceGraphs
+    from u2gnn_hip.synthetic import as_graph_store, collab_like
+    stores = {"mutag": lambda: GraphStore(util.load_data("MUTAG", False)[0]),
+              "ptc": lambda: GraphStore(util.load_data("PTC", False)[0]),
+              "c4": lambda: as_graph_store(collab_like(seed=0))}
+    for b in ("host", "device"):
+        DeviceGraphs.from_store(stores["mutag"](), "cuda", hops=2, build=b)
+    torch.cuda.synchronize()
+    out = []
+    for item in args.build.split(","):
+        name, H = item.split(":")
+        H = int(H)
+        row = {"store": name, "hops": H}
+        built = {}
+        for b in ("device", "host"):
+            store = stores[name]()                              # a fresh store: no cached hop lists
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            built[b] = DeviceGraphs.from_store(store, "cuda", hops=H, build=b, scratch_bytes=args.scratch_mb << 20)
+            torch.cuda.synchronize()
+            row[f"{b}_s"] = round(time.perf_counter() - t0, 3)
+        dv, hs = built["device"], built["host"]
+        row.update(graphs=dv.G, nodes=dv.V, entries=dv.E, chunks=dv.last_expand[0],
+                   scratch_mb=round(dv.last_expand[1] / 2 ** 20, 1), host_over_device=round(row["host_s"] / row["device_s"], 2),
+                   equal=bool(all(np.array_equal(dv.host[k], hs.host[k]) for k in dv.ARRAYS)
+                              and np.array_equal(dv.max_dist, hs.max_dist) and np.array_equal(dv.n_entries, hs.n_entries)))
+        out.append(row)
+        del built, dv, hs
+    print(json.dumps({"structure_builds": out}), flush=True)
+
+
 def distances_main(args):
     import util
     from u2gnn_hip.batching import GraphStore
     from u2gnn_hip.synthetic import as_graph_store, collab_like
     out = {"distances": args.distances, "csr_hops": args.csr_hops}
+    run = pair_pipeline if args.pipeline else distance_setting
     for which in args.settings.split(","):
         if which == "c4":
-            out["c4"] = distance_setting("C4 synthetic as a GraphStore", as_graph_store(collab_like(seed=0)), 3, 64, 16,
-                                         args)
+            out["c4"] = run("C4 synthetic as a GraphStore", as_graph_store(collab_like(seed=0)), 3, 64, 16, args)
         elif which == "mutag":
             graphs, C = util.load_data("MUTAG", False)
-            out["mutag"] = distance_setting("MUTAG", GraphStore(graphs), C, 64, 16, args)
+            out["mutag"] = run("MUTAG", GraphStore(graphs), C, 64, 16, args)
         else:
             raise SystemExit(f"unknown setting {which!r}")
     print(json.dumps(out), flush=True)
@@ -230,8 +366,14 @@ def main():
     ap.add_argument("--distances", type=int, default=0, help="H: measure attention='graphs' with distances=H instead")
     ap.add_argument("--settings", default="c4,mutag", help="with --distances: which of c4, mutag to run")
     ap.add_argument("--csr_hops", type=int, default=2, help="with --distances: the edges + hops route beside it")
+    ap.add_argument("--pipeline", action="store_true", help="with --distances: fresh batches, host against device")
+    ap.add_argument("--build", default="", help="instead: time DeviceGraphs.from_store(hops=H) on the host and on the "
+                                                "device for store:H items of c4, ptc, mutag")
+    ap.add_argument("--scratch_mb", type=int, default=256, help="with --build: the device build's dense scratch")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X: a timing without one would mean nothing"
+    if args.build:
+        return structure_builds(args)
     if args.distances:
         return distances_main(args)
     from pytorch_U2GNN_Sup import TransformerU2GNN
