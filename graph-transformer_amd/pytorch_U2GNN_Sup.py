@@ -33,14 +33,21 @@ seed and, without ``hops``, the state_dict keys are the reference's;
 nodes of its graph, and each encoder layer adds hop_bias[l][t][min(shortest-path distance, H)] to the score of a pair
 (index H also for a pair no path joins) -- Graphormer's spatial encoding on the per-graph kernels.  The same ONE more
 parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last); the batch carries the pair types as
-``DeviceBatch.pairs`` = ``PairTypes.from_store(store, graph_ids, N, device, H)``.
+``DeviceBatch.pairs`` = ``PairTypes.from_store(store, graph_ids, N, device, H)``;
+``centrality`` = None / 0, or D in [1, 63], with any ``attention``: Graphormer's centrality encoding -- the stack's input
+is X_concat[n] + degree_emb[min(degree of n, D)], one more parameter ``degree_emb`` [D + 1, feature_dim_size]
+(zeros, registered after every reference parameter and before ``hop_bias``), added inside the first gather, so every
+gathered row (the neighbour tokens of "neighbors" too) carries the vector of the node it was gathered from; the
+re-gather between U2GNN layers is untouched.  The batch carries the nodes' degrees as ``DeviceBatch.deg``
+(``from_offsets(..., degrees=store.degrees_of(graph_ids))`` or ``from_store(..., degrees=...)``; reference-style tensor
+inputs carry no edges, so ``forward`` raises a ValueError for them).
 """
 import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from u2gnn_hip.core import (DeviceBatch, FlatParams, SupCore, check_attention, check_distances, check_hops,
-                            hop_bias_last)
+from u2gnn_hip.core import (DeviceBatch, FlatParams, SupCore, check_attention, check_centrality, check_distances,
+                            check_hops, hop_bias_last)
 
 
 class _SupFunction(torch.autograd.Function):
@@ -63,7 +70,7 @@ class TransformerU2GNN(nn.Module):
 
     def __init__(self, feature_dim_size, ff_hidden_size, num_classes,
                  num_self_att_layers, dropout, num_U2GNN_layers, precision="fp32", attention="nodes", hops=None,
-                 distances=None):
+                 distances=None, centrality=None):
         super(TransformerU2GNN, self).__init__()
         self.feature_dim_size = feature_dim_size
         self.ff_hidden_size = ff_hidden_size
@@ -75,6 +82,7 @@ class TransformerU2GNN(nn.Module):
         self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
         self.distances = check_distances(distances, attention, hops)
+        self.centrality = check_centrality(centrality)
         # parameter containers built in the reference's order (identical init under a seed)
         self.u2gnn_layers = torch.nn.ModuleList()
         for _ in range(self.num_U2GNN_layers):
@@ -87,13 +95,15 @@ class TransformerU2GNN(nn.Module):
         for _ in range(self.num_U2GNN_layers):
             self.predictions.append(nn.Linear(self.feature_dim_size, self.num_classes))
             self.dropouts.append(nn.Dropout(dropout))
+        if self.centrality:   # after every reference parameter; zeros: torch's generator is not touched
+            self.degree_emb = nn.Parameter(torch.zeros(self.centrality + 1, self.feature_dim_size))
         if self.hops or self.distances:   # after every reference parameter; zeros: torch's generator is not touched
             self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers,
                                                      (self.hops or self.distances) + 1))
         self._core = None
 
     def named_parameters(self, prefix='', recurse=True, remove_duplicate=True):
-        """torch's, with hop_bias (registered last, but a parameter of the model itself) listed last."""
+        """torch's, with degree_emb and hop_bias (registered last, but parameters of the model itself) listed last."""
         return hop_bias_last(super().named_parameters(prefix, recurse, remove_duplicate), prefix)
 
     @property

@@ -24,7 +24,10 @@ with attention="edges": attention over the H-hop neighbourhood with a learned bi
 trainable parameter ``hop_bias`` [L, T, H + 1] (zeros, registered last), as in pytorch_U2GNN_Sup.  ``distances`` = None,
 or H in [1, 31] with attention="graphs" (not with ``hops``): attention over the whole graph with hop_bias[l][t][min(
 shortest-path distance, H)] on every pair's score (H also for unconnected pairs); the batch's ``pairs`` is
-``PairTypes.from_store(store, graph_ids, N, device, H)``, as in pytorch_U2GNN_Sup.
+``PairTypes.from_store(store, graph_ids, N, device, H)``, as in pytorch_U2GNN_Sup.  ``centrality`` = None / 0, or D in
+[1, 63], with any ``attention``: the stack's input is X_concat[n] + degree_emb[min(degree of n, D)], one more trainable
+parameter ``degree_emb`` [D + 1, feature_dim_size] (zeros, registered after every other parameter and before
+``hop_bias``); the batch must be a ``DeviceBatch`` with ``deg``, as in pytorch_U2GNN_Sup.
 """
 import math
 
@@ -34,7 +37,8 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from sampled_softmax import SampledSoftmax
 from u2gnn_hip import kernels as K
-from u2gnn_hip.core import DeviceBatch, check_attention, check_distances, check_hops, hop_bias_last
+from u2gnn_hip.core import (DeviceBatch, check_attention, check_centrality, check_distances, check_hops,
+                            hop_bias_last)
 from u2gnn_hip.engine import site_seed
 from u2gnn_hip.unsup import SITE_SS_DROP, UnSupCore
 
@@ -76,7 +80,7 @@ class TransformerU2GNN(nn.Module):
     def __init__(self, vocab_size, feature_dim_size, ff_hidden_size, sampled_num,
                  num_self_att_layers, num_U2GNN_layers, dropout, device, sampler_type='default',
                  loss_type='default', adj_mat=None, single_layer_only=True, precision="fp32", attention="nodes",
-                 hops=None, distances=None):
+                 hops=None, distances=None, centrality=None):
         super(TransformerU2GNN, self).__init__()
         if sampler_type != 'default' or loss_type != 'default':
             raise NotImplementedError("only sampler_type='default', loss_type='default' (graph-level U2GNN) "
@@ -85,6 +89,7 @@ class TransformerU2GNN(nn.Module):
         self.attention = check_attention(attention)
         self.hops = check_hops(hops, attention)
         self.distances = check_distances(distances, attention, hops)
+        self.centrality = check_centrality(centrality)
         self.self_attn = nn.MultiheadAttention(self.feature_dim_size, 1, dropout=dropout)
         self.ff_hidden_size = ff_hidden_size
         self.num_self_att_layers = num_self_att_layers
@@ -108,6 +113,8 @@ class TransformerU2GNN(nn.Module):
         self.ss = SampledSoftmax(self.vocab_size, self.sampled_num, self.feature_dim_size * self.num_U2GNN_layers,
                                  self.device)
         self.reset_parameters()
+        if self.centrality:   # after every other parameter; zeros: torch's generator is not touched
+            self.degree_emb = nn.Parameter(torch.zeros(self.centrality + 1, self.feature_dim_size))
         if self.hops or self.distances:   # after every other parameter; zeros: torch's generator is not touched
             self.hop_bias = nn.Parameter(torch.zeros(self.num_U2GNN_layers, self.num_self_att_layers,
                                                      (self.hops or self.distances) + 1))
@@ -118,7 +125,7 @@ class TransformerU2GNN(nn.Module):
         self.weight.data.uniform_(-stdv, stdv)
 
     def named_parameters(self, prefix='', recurse=True, remove_duplicate=True):
-        """torch's, with hop_bias (registered last, but a parameter of the model itself) listed last."""
+        """torch's, with degree_emb and hop_bias (registered last, but parameters of the model itself) listed last."""
         return hop_bias_last(super().named_parameters(prefix, recurse, remove_duplicate), prefix)
 
     @property
@@ -128,9 +135,10 @@ class TransformerU2GNN(nn.Module):
         return self._core
 
     def trainable_names(self):
-        """Parameters on the loss path (encoders + ss.weight, and hop_bias with ``hops`` or ``distances``)."""
+        """Parameters on the loss path (encoders + ss.weight, degree_emb with ``centrality`` and hop_bias with ``hops``
+        or ``distances``)."""
         return [n for n, _ in self.named_parameters()
-                if n.startswith("u2gnn_layers.") or n in ("ss.weight", "hop_bias")]
+                if n.startswith("u2gnn_layers.") or n in ("ss.weight", "degree_emb", "hop_bias")]
 
     def forward(self, X_concat, input_x, input_y, args=None):
         if isinstance(X_concat, DeviceBatch):

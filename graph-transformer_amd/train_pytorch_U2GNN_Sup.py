@@ -10,7 +10,7 @@ Execution: the default trainer is the fused HIP step (u2gnn_hip.train.SupTrainer
 backward into a flat grad buffer, device-side clip + Adam, no per-step host sync except the loss
 readout the reference also does).  ``--autograd`` runs the reference's exact loop instead
 (model(), cross_entropy, loss.backward(), clip_grad_norm_, torch Adam, StepLR) — on the same kernels.
-Extra flags: --precision, --attention, --hops, --distances, --autograd, --max_steps (0 = full epochs), --world_size /
+Extra flags: --precision, --attention, --hops, --distances, --centrality, --autograd, --max_steps (0 = full epochs), --world_size /
 --dist_backend (data parallelism, u2gnn_hip.cli: one process per GPU, a global step = world_size
 consecutive batches of the single stream with the averaged gradient, RCCL all-reduce under the backward).
 """
@@ -64,6 +64,10 @@ parser.add_argument("--distances", default=0, type=int,
                          "(clipped at this many bonds, 1..31; unconnected pairs take the last entry) to the scores of "
                          "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
                          "--adjacency says where each batch's distances are searched")
+parser.add_argument("--centrality", default=0, type=int,
+                    help="with any --attention: a learned vector per node degree (0 .. this many, 1..63; larger "
+                         "degrees take the last) added to every node's input features (one more parameter, "
+                         "degree_emb); 0 = off")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
                     help="where each batch's adjacency (--attention edges) or pair distances (--attention graphs "
                          "--distances) are built: device = on the GPU from a per-dataset structure kept there (built "
@@ -90,6 +94,8 @@ if args.distances and args.hops:
     parser.error("--distances and --hops exclude each other")
 if not 0 <= args.distances <= 31:
     parser.error("--distances must be in 0..31")
+if not 0 <= args.centrality <= 63:
+    parser.error("--centrality must be in 0..63")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -131,13 +137,15 @@ model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.
                          num_classes=num_classes, dropout=args.dropout, num_self_att_layers=args.num_timesteps,
                          num_U2GNN_layers=args.num_hidden_layers, precision=args.precision,
                          attention=args.attention, hops=args.hops or None,
-                         distances=args.distances or None).to(device)
+                         distances=args.distances or None, centrality=args.centrality or None).to(device)
 num_batches_per_epoch = int((len(train_graphs) - 1) / args.batch_size) + 1
 # global steps per epoch: each consumes world_size batches of the stream
 steps_per_epoch = -(-num_batches_per_epoch // run.world)
 
 
 train_X = torch.from_numpy(train_store.X).to(device)
+# --centrality: the train store's node degrees beside its features, uploaded once (a batch gathers its rows' on the GPU)
+train_deg = torch.from_numpy(train_store.deg.astype(np.int32)).to(device) if args.centrality else None
 # --adjacency device: each store's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
 edges = args.attention == "edges"
 graphs_of = {id(s): device_graphs(s, device, args.hops, args.adjacency, log, distances=args.distances)
@@ -148,9 +156,10 @@ def to_device(hb, store=train_store):
     dg = graphs_of[id(store)]
     if hb.X_concat is None:
         b = DeviceBatch.from_store(hb, train_X, device=device, graphs=dg,
-                                   distances=(args.distances or None) if dg is not None else None)
+                                   distances=(args.distances or None) if dg is not None else None, degrees=train_deg)
     else:
-        b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device)
+        b = DeviceBatch.from_offsets(hb.input_x, hb.offsets, hb.X_concat, hb.labels, device=device,
+                                     degrees=store.degrees_of(hb.graph_ids) if args.centrality else None)
         if dg is not None and args.distances:
             b.pairs = dg.pair_types(hb.graph_ids, args.distances, b.rowptr)
         elif dg is not None:

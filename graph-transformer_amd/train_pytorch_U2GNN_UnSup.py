@@ -9,7 +9,7 @@ LogisticRegression(liblinear, tol=1e-3) (:164-188), stdout line (:207) and acc f
 (<run_folder>/../runs_pytorch_U2GNN_UnSup/<model_name>/checkpoints/model_acc.txt).
 
 The fork's file cannot run as shipped; this runs its working semantics
-(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --hops, --distances, --max_steps,
+(pytorch_U2GNN_UnSup.TransformerU2GNN of this package).  Extra flags: --precision, --attention, --hops, --distances, --centrality, --max_steps,
 --world_size / --dist_backend (data parallelism, u2gnn_hip.cli: rank r trains batch r of each global step
 with the r-th sample draw of the step; encoder gradients all-reduced, the touched ss.weight rows
 all-gathered, dp.UnSupGradSync).
@@ -66,6 +66,10 @@ parser.add_argument("--distances", default=0, type=int,
                          "all pairs of a graph (one more parameter, hop_bias); 0 = off.  Not together with --hops; "
                          "--adjacency says where each batch's distances are searched.  Not with --world_size > 1, as "
                          "--hops")
+parser.add_argument("--centrality", default=0, type=int,
+                    help="with any --attention: a learned vector per node degree (0 .. this many, 1..63; larger "
+                         "degrees take the last) added to every node's input features (one more parameter, "
+                         "degree_emb); 0 = off.  Not with --world_size > 1, as --hops")
 parser.add_argument("--adjacency", default="device", choices=["device", "host"],
                     help="where each batch's adjacency (--attention edges) or pair distances (--attention graphs "
                          "--distances) are built: device = on the GPU from a per-dataset structure kept there (built "
@@ -94,6 +98,10 @@ if not 0 <= args.distances <= 31:
     parser.error("--distances must be in 0..31")
 if args.distances and (args.world_size > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
     parser.error("--distances is not available with --world_size > 1 in the unsupervised trainer")
+if not 0 <= args.centrality <= 63:
+    parser.error("--centrality must be in 0..63")
+if args.centrality and (args.world_size > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+    parser.error("--centrality is not available with --world_size > 1 in the unsupervised trainer")
 
 _rc = self_launch(args.world_size, __file__, sys.argv[1:])   # before anything touches the GPU
 if _rc is not None:
@@ -128,6 +136,8 @@ if reddit:
     feature_dim_size = 4
 store = GraphStore(graphs, reddit_tile=4 if reddit else 0)
 store_X = torch.from_numpy(store.X).to(device)
+# --centrality: the store's node degrees beside its features, uploaded once (a batch gathers its rows' on the GPU)
+store_deg = torch.from_numpy(store.deg.astype(np.int32)).to(device) if args.centrality else None
 # --adjacency device: the dataset's adjacency as per-graph pieces on the GPU (None: built per batch on the host)
 store_graphs = (device_graphs(store, device, args.hops, args.adjacency, log, distances=args.distances)
                 if args.attention == "edges" or args.distances else None)
@@ -141,7 +151,7 @@ model = TransformerU2GNN(feature_dim_size=feature_dim_size, ff_hidden_size=args.
                          vocab_size=vocab_size, sampled_num=args.sampled_num,
                          num_U2GNN_layers=args.num_hidden_layers, device=device, precision=args.precision,
                          attention=args.attention, hops=args.hops or None,
-                         distances=args.distances or None).to(device)
+                         distances=args.distances or None, centrality=args.centrality or None).to(device)
 trainer = UnSupTrainer(model, lr=args.learning_rate, max_norm=0.5)
 if run.world > 1:
     broadcast_params(trainer.flat)
@@ -165,7 +175,8 @@ def train():
             break
         hb, index = run.next_batch(batch_nodes)   # this rank's batch of the next global step
         b = DeviceBatch.from_store(hb, store_X, device=device, graphs=store_graphs,
-                                   distances=(args.distances or None) if store_graphs is not None else None)
+                                   distances=(args.distances or None) if store_graphs is not None else None,
+                                   degrees=store_deg)
         if args.attention == "edges" and b.adj is None:   # the batch's adjacency (plus the diagonal; --hops: the H-hop lists)
             b.adj = Adjacency.from_store(store, hb.graph_ids, b.N, device, args.hops)
         if args.distances and b.pairs is None:   # the batch's pair types: the graphs' cached blocks, concatenated and copied

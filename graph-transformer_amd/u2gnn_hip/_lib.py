@@ -162,6 +162,9 @@ _HIP_SIGS = {
     "u2gnn_abi_version": ([], c_int32),
     "u2gnn_gather_rows": ([VP, I64, I64, VP, I64, VP, I64, I64, I64, I64, I64, VP, VP], c_int32),
     "u2gnn_scatter_add_rows": ([VP, I64, VP, I64, VP, I64, I64, I64, I64, VP, VP], c_int32),
+    "u2gnn_gather_rows_emb": ([VP, I64, I64, VP, I64, VP, I64, I64, I64, I64, I64, VP, VP, I64, I32, VP, VP], c_int32),
+    "u2gnn_class_rows_grad_ws_floats": ([I64, I64, I32], I64),
+    "u2gnn_class_rows_grad": ([VP, I64, I64, I64, VP, I64, VP, I64, I32, VP, I64, VP, I64, VP], c_int32),
     "u2gnn_gemm": ([POINTER(GemmArgs), VP], c_int32),
     "u2gnn_gemm_group": ([POINTER(GemmArgs), I32, VP], c_int32),
     "u2gnn_reduce_batch_ws_floats": ([POINTER(ReduceJob), I32], I64),

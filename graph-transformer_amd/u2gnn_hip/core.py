@@ -25,7 +25,7 @@ from .engine import (SITE_ATTN, SITE_DROP1, SITE_DROP2, SITE_DROPFF, SITE_HEAD, 
                      OffPath, encoder_layer_backward, encoder_layer_forward, rup, side_stream_pays, site_seed)
 # (Adjacency, check_hops, ATTENTION_MODES: re-exported, the models, tools and tests import them from here)
 from .pattern import (ATTENTION_MODES, NODES, Adjacency, AttnPattern, DeviceGraphs, PairTypes,  # noqa: F401
-                      check_attention, check_distances, check_hops)
+                      check_attention, check_centrality, check_distances, check_hops)
 
 
 _IOTA = {}
@@ -79,6 +79,10 @@ class DeviceBatch:
     # the same integers searched on the GPU (from_store(..., graphs=DeviceGraphs, distances=H)); the other modes never
     # read it
     pairs: Optional[PairTypes] = None
+    # the rows' node degrees, int32 [N], raw (the kernels clip): what ``centrality`` indexes the model's degree_emb with
+    # -- from_offsets(..., degrees=store.degrees_of(graph_ids)) or from_store(..., degrees=the store's on the device);
+    # without ``centrality`` nothing reads it
+    deg: Optional[torch.Tensor] = None
 
     def __post_init__(self):
         if self.err is None:
@@ -94,9 +98,10 @@ class DeviceBatch:
         return self.input_x.stride(0)
 
     @staticmethod
-    def from_offsets(input_x, offsets, X_concat, labels=None, device="cuda", input_y=None):
+    def from_offsets(input_x, offsets, X_concat, labels=None, device="cuda", input_y=None, degrees=None):
         """Host arrays (numpy / torch CPU) -> HBM.  Block-diagonal graph_pool of ones given by
-        node offsets (train_pytorch_U2GNN_Sup.py:73-89)."""
+        node offsets (train_pytorch_U2GNN_Sup.py:73-89).  degrees: the rows' node degrees (a host array of N integers,
+        GraphStore.degrees_of(graph_ids)) -> ``deg``."""
         dev = torch.device(device)
         _check_range_host(input_x, int(np.asarray(offsets)[-1]))
         ix = torch.as_tensor(input_x, dtype=torch.int64).to(dev, non_blocking=True).contiguous()
@@ -106,12 +111,17 @@ class DeviceBatch:
         B = off.numel() - 1
         lab = None if labels is None else torch.as_tensor(labels, dtype=torch.int64).to(dev, non_blocking=True)
         iy = None if input_y is None else torch.as_tensor(input_y, dtype=torch.int64).to(dev, non_blocking=True)
+        deg = None
+        if degrees is not None:
+            deg = torch.as_tensor(np.asarray(degrees).astype(np.int32)).to(dev, non_blocking=True).contiguous()
+            if deg.shape != (N,):
+                raise ValueError(f"degrees: one per row, {N}, got {tuple(deg.shape)}")
         return DeviceBatch(N, B, ix, X, off.to(dev), torch.arange(N, device=dev, dtype=torch.int64),
                            torch.ones(N, device=dev, dtype=torch.float32), lab, iy, block_rows=True,
-                           rows_contiguous=True)
+                           rows_contiguous=True, deg=deg)
 
     @staticmethod
-    def from_store(hb, X_dev: torch.Tensor, device="cuda", graphs=None, distances=None):
+    def from_store(hb, X_dev: torch.Tensor, device="cuda", graphs=None, distances=None, degrees=None):
         """A natively assembled batch (GraphStore.assemble(..., gather_x=False)) -> HBM: input_x, offsets
         and the rows' dataset node ids cross PCIe asynchronously from page-locked buffers (~0.7 MB at
         C4 instead of the 7 MB X_concat; BatchLoader assembles straight into a ring of them);
@@ -122,11 +132,16 @@ class DeviceBatch:
         arrays above, the row offsets are the batch's own, and the kernel runs beside the feature gather.
         distances = H (with ``graphs`` a structure built without hops): the batch gets its pair types instead (``pairs``,
         attention="graphs" with distances=H, no ``adj``), searched on the GPU from the one-hop structure
-        (DeviceGraphs.launch_pairs) in the same place: ids and pair offsets travel with the arrays above."""
+        (DeviceGraphs.launch_pairs) in the same place: ids and pair offsets travel with the arrays above.
+        degrees: the store's node degrees resident on the device (int32 [V], uploaded once per dataset from store.deg):
+        the batch's rows of it are gathered beside the features -> ``deg`` (``centrality``)."""
         from . import kernels as K
         if distances and graphs is None:
             raise ValueError("distances: the pair types are searched from graphs=DeviceGraphs (built without hops)")
         dev = torch.device(device)
+        if degrees is not None and (degrees.dtype != torch.int32 or degrees.shape != (X_dev.shape[0],)
+                                    or degrees.device != X_dev.device):
+            raise ValueError("degrees: int32 [V] beside X_dev (torch.from_numpy(store.deg.astype(np.int32)).to(device))")
         N, B = int(hb.offsets[-1]), len(hb.offsets) - 1
         slot = getattr(hb, "pinned", None)
         _check_range_host(hb.input_x, N)
@@ -156,6 +171,7 @@ class DeviceBatch:
                 X = torch.empty(N, d, device=dev, dtype=torch.float32)
                 if N:
                     K.gather_rows(X_dev, gnode, 1, X, N, N, d, d)
+                deg = degrees[gnode] if degrees is not None else None
                 err = torch.zeros(1, device=dev, dtype=torch.int32)
                 adj = pairs = None
                 if distances:
@@ -166,6 +182,8 @@ class DeviceBatch:
             ready.record(cs)
             main.wait_event(ready)
             used = [ix, gnode, off, lab, X, err]   # allocated on the copy stream, used on the compute one
+            if deg is not None:
+                used.append(deg)
             if adj is not None:   # (the adjacency's five arrays are views of one buffer, rowptr its start)
                 used += [gid, ent_off, adj.rowptr] + ([adj.etype] if adj.etype is not None else [])
             if pairs is not None:   # (pair_off is ent_off)
@@ -175,7 +193,7 @@ class DeviceBatch:
             iy = gnode if hb.input_y is not None else None
             colidx, vals = _pool_iota(N, dev)
             return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, err, block_rows=True, rows_contiguous=True,
-                               adj=adj, pairs=pairs)
+                               adj=adj, pairs=pairs, deg=deg)
         if slot is not None:
             k1 = hb.input_x.shape[1]
             h2d = lambda t: t.to(dev, non_blocking=True)  # noqa: E731
@@ -200,7 +218,7 @@ class DeviceBatch:
         elif graphs is not None:
             adj = graphs.adjacency(hb.graph_ids, off)
         return DeviceBatch(N, B, ix, X, off, colidx, vals, lab, iy, block_rows=True, rows_contiguous=True, adj=adj,
-                           pairs=pairs)
+                           pairs=pairs, deg=degrees[gnode] if degrees is not None else None)
 
     @staticmethod
     def from_reference_inputs(input_x, graph_pool, X_concat, labels=None):
@@ -230,19 +248,23 @@ def _check_range_host(input_x, N: int):
         raise IndexError("index out of range in self (input_x entry outside [0, N))")
 
 
+TRAILING = ("degree_emb", "hop_bias")   # the models' own trailing parameters, in flat-buffer order
+
+
 def hop_bias_last(named, prefix: str = ""):
-    """A model's named_parameters() with ``hop_bias`` moved to the end.  torch lists a module's own parameters before
-    its children's, which would put hop_bias first; last, every other parameter keeps its place in the flat buffer
-    (FlatParams) and the region after the last encoder layer ends where hop_bias begins (dp.OverlappedGradAllReduce)."""
-    key = (prefix + "." if prefix else "") + "hop_bias"
-    held = None
+    """A model's named_parameters() with its own trailing parameters moved to the end: ..., ``degree_emb``, ``hop_bias``
+    (TRAILING; whichever exist).  torch lists a module's own parameters before its children's, which would put them
+    first; last, every other parameter keeps its place in the flat buffer (FlatParams) and the region after the last
+    encoder layer ends where the first of them begins (dp.OverlappedGradAllReduce)."""
+    keys = {(prefix + "." if prefix else "") + k: i for i, k in enumerate(TRAILING)}
+    held = {}
     for n, p in named:
-        if n == key:
-            held = (n, p)
+        if n in keys:
+            held[keys[n]] = (n, p)
         else:
             yield n, p
-    if held is not None:
-        yield held
+    for i in sorted(held):
+        yield held[i]
 
 
 class EncoderStack:
@@ -251,16 +273,21 @@ class EncoderStack:
 
     def __init__(self, u2gnn_layers, d: int, ff: int, T: int, L: int, prec: str = "fp32", p_enc: float = 0.5,
                  attention: str = "nodes", hops: Optional[int] = None, hop_bias=None,
-                 distances: Optional[int] = None):
+                 distances: Optional[int] = None, centrality: Optional[int] = None, degree_emb=None):
         """hops = H with attention="edges", or distances = H with attention="graphs": every layer adds
         hop_bias()[l][t][type] to its attention scores, type = the distance of an adjacency entry (hops) or the clipped
         distance of a pair of the graph (distances); hop_bias: a callable that returns the model's [L, T, H + 1]
-        parameter (read where it lies at each forward)."""
+        parameter (read where it lies at each forward).
+        centrality = D (any attention): the stack's input is X_concat[n] + degree_emb()[min(deg[n], D)] (the batch's
+        ``deg``), added inside the first gather; degree_emb: a callable that returns the model's [D + 1, d] parameter
+        (read where it lies); the backward then takes layer (0, 0)'s input gradient and reduces it per degree class
+        into grads["degree_emb"]."""
         self.layers, self.d, self.ff, self.T, self.L, self.prec, self.p_enc = u2gnn_layers, d, ff, T, L, prec, p_enc
         self.attention = check_attention(attention)
         self.hops, self.hop_bias = check_hops(hops, attention), hop_bias
         self.distances = check_distances(distances, attention, hops)
         self.n_types = (self.hops or self.distances or 0) + 1   # the width of a hop_bias table (1: no tables)
+        self.centrality, self.degree_emb = check_centrality(centrality), degree_emb
         self.packed = None
         # Python orchestration only: the three-pass attention forward where the fused kernel would run
         # (tools/prec_train_probe.py)
@@ -274,7 +301,8 @@ class EncoderStack:
         """The stack of a model module; encoder dropout is hard-coded to 0.5 (pytorch_U2GNN_Sup.py:20)."""
         return cls(module.u2gnn_layers, module.feature_dim_size, module.ff_hidden_size, module.num_self_att_layers,
                    module.num_U2GNN_layers, precision, 0.5, getattr(module, "attention", "nodes"),
-                   getattr(module, "hops", None), lambda: module.hop_bias, getattr(module, "distances", None))
+                   getattr(module, "hops", None), lambda: module.hop_bias, getattr(module, "distances", None),
+                   getattr(module, "centrality", None), lambda: module.degree_emb)
 
     def layer_params(self, l, t) -> LayerParams:
         return LayerParams.from_encoder_layer(self.layers[l].layers[t])
@@ -343,6 +371,20 @@ class EncoderStack:
         types under ``distances``."""
         return pattern.what.etype if pattern.kind == "csr" else pattern.pairs.etype
 
+    def _degrees(self, b: "DeviceBatch"):
+        """The batch's degrees for ``centrality`` (validated) and the table where it lies."""
+        if b.deg is None:
+            raise ValueError("centrality needs the batch's node degrees: DeviceBatch.from_offsets(..., degrees="
+                             "store.degrees_of(graph_ids)) or from_store(..., degrees=the store's int32 degrees on the "
+                             "device), or set DeviceBatch.deg (int32 [N]) (reference-style tensor inputs carry no "
+                             "edges)")
+        if b.deg.dtype != torch.int32 or b.deg.shape != (b.N,) or not b.deg.is_contiguous():
+            raise ValueError(f"centrality: DeviceBatch.deg must be contiguous int32 [{b.N}]")
+        table = self.degree_emb().detach()
+        if table.shape != (self.centrality + 1, self.d):
+            raise ValueError(f"centrality={self.centrality}: degree_emb must be [{self.centrality + 1}, {self.d}]")
+        return b.deg, table
+
     def forward(self, b: "DeviceBatch", train: bool, need_ctx: bool, seed: int):
         """Returns (outs, ctx): outs[l] = padded [Np, dp] slot-0 output of U2GNN layer l."""
         pattern, W, stride = self._pattern(b)
@@ -364,7 +406,10 @@ class EncoderStack:
         self._pack(dev)
         slot0 = torch.arange(b.N, device=dev, dtype=torch.int64) * W if W > 1 else None
         X = torch.empty(Rp, dp, device=dev, dtype=torch.float32)
-        K.gather_rows(b.X_concat, b.input_x, stride, X, R, Rp, d, dp, b.err)
+        if self.centrality:   # the table row of each gathered node's degree added on the way: still one launch
+            K.gather_rows_emb(b.X_concat, b.input_x, stride, X, R, Rp, d, dp, *self._degrees(b), b.err)
+        else:
+            K.gather_rows(b.X_concat, b.input_x, stride, X, R, Rp, d, dp, b.err)
         outs, lctxs = [], []
         for l in range(self.L):
             lctx = []
@@ -410,7 +455,8 @@ class EncoderStack:
     def backward(self, ctx, ext_grad, grads: dict, prefix: str = "u2gnn_layers"):
         """ext_grad(l) -> fresh padded gradient of outs[l] from outside the stack (head / loss).
         Writes encoder parameter gradients into grads[<reference key>]; returns None (the stack
-        input, rows of X_concat, takes no gradient)."""
+        input, rows of X_concat, takes no gradient) -- with ``centrality`` the gradient of the stack's input rows,
+        after reducing it per degree class into grads["degree_emb"]."""
         b = ctx["batch"]
         ldims, stride, slot0 = ctx["ldims"], ctx["stride"], ctx["slot0"]
         dnext = None
@@ -433,8 +479,10 @@ class EncoderStack:
                 pre = f"{prefix}.{l}.layers.{t}."
                 g = LayerParams(*[grads[pre + k] for k in LAYER_KEYS])
                 lc = ctx["layers"][l][t]
-                # the stack's input (gathered X_concat rows) is not trainable: no dX out of layer (0, 0)
-                need_dx = l > 0 or t > 0
+                # the stack's input (gathered X_concat rows) is not trainable: no dX out of layer (0, 0) -- unless
+                # ``centrality`` adds its table to it.  (That layer then writes its parameter gradients on the side
+                # stream after the fork, as every layer with an input gradient does: _layer_grads_done)
+                need_dx = l > 0 or t > 0 or bool(self.centrality)
                 if isinstance(lc, native.NativeCtx):
                     dX = native.layer_backward(dX, lc, self.packed[l][t], self.layer_params(l, t), g, ldims,
                                                self.prec, side=off.side, deep_wgrad=engine_deep_wgrad(),
@@ -448,6 +496,8 @@ class EncoderStack:
             dnext = dX
         if dbias_all is not None:
             K.bias_table_grad(dbias_all, etype, grads["hop_bias"].view(self.L * self.T, self.n_types))
+        if self.centrality:   # d degree_emb[c] = the sum of layer (0, 0)'s input-gradient rows of class c (this stream)
+            K.class_rows_grad(dnext, b.input_x, stride, b.deg, b.N, ldims.N, self.d, grads["degree_emb"])
         off.join()   # parameter gradients complete before the caller's optimizer reads them
         return dnext
 

@@ -115,11 +115,13 @@ class OverlappedGradAllReduce:
                   for n in flat.names if n.startswith(layer_prefix) and ".layers." in n}
         self.n_layers = len(layers)
         enc_hi = max((b for n, (a, b) in self.span.items() if n.startswith(layer_prefix)), default=0)
-        # [head parameters, end): what is complete before the encoder backward starts.  hop_bias (the last parameter of
-        # a model with hops) is not: its gradient is reduced from all layers after the last one's backward, so the
-        # tail ends where it begins and its region goes out with the leftovers in __call__, on the step's stream
-        # after that reduction
-        tail_hi = self.span["hop_bias"][0] if "hop_bias" in self.span else flat.gflat.numel()
+        # [head parameters, end): what is complete before the encoder backward starts.  The models' trailing parameters
+        # (core.TRAILING: degree_emb with centrality, hop_bias with hops / distances) are not: their gradients are
+        # reduced after the last layer's backward (from its input gradient; from all layers' bias gradients), so the
+        # tail ends where the first of them begins and their regions go out with the leftovers in __call__, on the
+        # step's stream after those reductions
+        from .core import TRAILING
+        tail_hi = min((self.span[n][0] for n in TRAILING if n in self.span), default=flat.gflat.numel())
         self.tail = (self._align_end(enc_hi), max(tail_hi, self._align_end(enc_hi)))
         self.acc: Optional[Tuple[int, int]] = None
         self.acc_stream = None

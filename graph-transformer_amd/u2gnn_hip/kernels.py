@@ -192,6 +192,51 @@ def gather_rows(src, idx, idx_stride, dst, n_rows, n_rows_pad, d, d_pad, err=Non
                                       _s()), "u2gnn_gather_rows")
 
 
+CLASS_ROWS_MAX = 64      # u2gnn_hip.h U2GNN_CLASS_ROWS_MAX: the classes (table rows) u2gnn_class_rows_grad reduces
+CLASS_ROWS_CHUNK = 256   # U2GNN_CLASS_ROWS_CHUNK: the consecutive rows one block of its first stage sums
+
+
+def class_rows_k(n_rows: int) -> int:
+    """U2GNN_CLASS_ROWS_K: the sequential adds plus tree levels a value of class_rows_grad passes through at most."""
+    chunks = -(-int(n_rows) // CLASS_ROWS_CHUNK)
+    return CLASS_ROWS_CHUNK // 4 + 2 + -(-chunks // 16) + 4
+
+
+def _class_table(deg, emb, src_rows, what):
+    if (deg.dtype != torch.int32 or not deg.is_contiguous() or deg.numel() < src_rows or emb.dtype != torch.float32
+            or emb.dim() != 2 or emb.stride(1) != 1):
+        raise _lib.U2GNNNativeError(f"{what}: deg int32 [src rows] contiguous, the table float32 [classes, d] row-major")
+
+
+def gather_rows_emb(src, idx, idx_stride, dst, n_rows, n_rows_pad, d, d_pad, deg, emb, err=None):
+    """gather_rows with emb[clamp(deg[s], 0, classes - 1)] added to the row gathered from source row s (deg int32
+    [src rows], emb f32 [classes, >= d], read where it lies); one launch."""
+    _dev(src, idx, dst, deg, emb)
+    _class_table(deg, emb, src.shape[0], "gather_rows_emb")
+    check(hip_lib().u2gnn_gather_rows_emb(_p(src), src.stride(0), src.shape[0], _p(idx), int(idx_stride), _p(dst),
+                                          dst.stride(0), int(n_rows), int(n_rows_pad), int(d), int(d_pad), _p(deg),
+                                          _p(emb), emb.stride(0) if emb.shape[0] > 1 else emb.shape[1],
+                                          int(emb.shape[0]), _p(err), _s()), "u2gnn_gather_rows_emb")
+
+
+def class_rows_grad(dX, idx, idx_stride, deg, src_rows, n_rows, d, demb):
+    """demb[c, :d] = the sum of the rows i < n_rows of dX whose class clamp(deg[idx[i * idx_stride]], 0, classes - 1)
+    is c (demb f32 [classes, >= d]; every entry stored, deterministic: two launches through a workspace)."""
+    _dev(dX, idx, deg, demb)
+    _class_table(deg, demb, src_rows, "class_rows_grad")
+    if dX.dtype != torch.float32 or dX.dim() != 2 or dX.stride(1) != 1 or dX.shape[0] < n_rows:
+        raise _lib.U2GNNNativeError("class_rows_grad: dX float32 row-major with at least n_rows rows")
+    n_classes = int(demb.shape[0])
+    n = hip_lib().u2gnn_class_rows_grad_ws_floats(int(n_rows), int(d), n_classes)
+    if n < 0:
+        raise _lib.U2GNNNativeError(f"class_rows_grad: 1..{CLASS_ROWS_MAX} classes and d >= 1, got {n_classes}, {d}")
+    ws = torch.empty(max(int(n), 1), device=dX.device, dtype=torch.float32)
+    check(hip_lib().u2gnn_class_rows_grad(_p(dX), dX.stride(0) if dX.shape[0] > 1 else dX.shape[1], int(n_rows),
+                                          int(d), _p(idx), int(idx_stride), _p(deg), int(src_rows), n_classes,
+                                          _p(demb), demb.stride(0) if n_classes > 1 else demb.shape[1], _p(ws),
+                                          ws.numel(), _s()), "u2gnn_class_rows_grad")
+
+
 def scatter_add_rows(src, idx, idx_stride, dst, n_rows, d, err=None):
     """dst[idx[i]] += src[i] for i < n_rows; out-of-range indices are skipped and flag err (int32[1])."""
     _dev(src, idx, dst)

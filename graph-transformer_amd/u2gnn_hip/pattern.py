@@ -54,6 +54,21 @@ def check_distances(distances, attention: str, hops=None) -> Optional[int]:
     return int(distances)
 
 
+CENTRALITY_MAX = 63   # degree classes 0 .. D of a centrality table: D + 1 <= U2GNN_CLASS_ROWS_MAX (u2gnn_hip.h)
+
+
+def check_centrality(centrality) -> Optional[int]:
+    """The ``centrality`` keyword of the models: None or 0 (off), or a D in [1, 63] -- a learned vector per node degree
+    0 .. D (larger degrees take D's) added to the stack's input.  Any attention mode."""
+    import numbers
+    if centrality is None:
+        return None
+    if isinstance(centrality, bool) or not isinstance(centrality, numbers.Integral) or \
+            not 0 <= int(centrality) <= CENTRALITY_MAX:
+        raise ValueError(f"centrality must be None, 0 or an integer in [1, {CENTRALITY_MAX}], got {centrality!r}")
+    return int(centrality) or None
+
+
 class PairTypes:
     """The pair types of attention="graphs" with ``distances`` on the device: graph b of the batch owns the entries
     pair_off[b] .. pair_off[b+1]-1 of etype, its [n_b, n_b] block row-major (GraphStore.distances): etype[pair_off[b] +

@@ -931,6 +931,39 @@ int u2gnn_adam_dev(float *param, const float *grad, float *exp_avg, float *exp_a
                    const float *sqnorm, float max_norm, double beta1, double beta2, float eps,
                    const double *lr, const int64_t *step, void *stream);
 
+/* ---- the centrality encoding (csrc/centrality.hip; ABI 19 grew by these entry points, nothing else changed):
+ * a learned table emb [n_classes][ld_emb >= d], one row per node degree, added to the stack's input on its way
+ * through the first gather, and the table's gradient.
+ * u2gnn_gather_rows_emb: u2gnn_gather_rows with dst[i, 0:d] = src[s, 0:d] + emb[clamp(deg[s], 0, n_classes - 1), 0:d],
+ * s = idx[i * idx_stride], deg: DEVICE int32 [src_rows] (raw degrees: the clipping happens here).  One IEEE add per
+ * element; padding columns and rows are zero; an out-of-range s gives a zero row and sets *err = 1, as the gather
+ * does.  One launch on the gather's own routes (16-byte rows with float4 accesses -- the table's rows 16-byte aligned
+ * too, else the next route --, the multi-row XCD-ordered kernel for d_pad <= 512, lane-consecutive dwords up to
+ * d_pad 1024, the plain loop beyond).  emb is read at launch where it lies.  Null emb, n_classes < 1, ld_emb < d:
+ * U2GNN_E_ARG.
+ * u2gnn_class_rows_grad: demb[c, 0:d] = sum over the rows i < n_rows whose class is c of dX[i, 0:d]; the class of row i
+ * is clamp(deg[idx[i * idx_stride]], 0, n_classes - 1), and a row whose index lies outside [0, src_rows) contributes
+ * nothing.  Every demb[c < n_classes][0:d] is stored (0 for a class without rows): the caller never zero-fills.
+ * Deterministic, no atomics, two launches: blocks sum U2GNN_CLASS_ROWS_CHUNK consecutive rows x 64 columns per class
+ * (4 row lanes, each a chain of CHUNK / 4 adds in row order, then a 2-level tree) into ws, then the chunks' partial
+ * sums are combined (16 lanes, each a chain over every 16th chunk in order, then a 4-level tree).  No value passes
+ * through more than U2GNN_CLASS_ROWS_K(n_rows) = 64 + 2 + ceil(ceil(n_rows / 256) / 16) + 4 sequential adds and tree
+ * levels, in an order the shapes alone fix.  ws: u2gnn_class_rows_grad_ws_floats(n_rows, d, n_classes) floats
+ * (host-only; -1 for arguments the call refuses).  Null pointers, n_classes outside [1, U2GNN_CLASS_ROWS_MAX], d < 1,
+ * ld < d, ld_demb < d, a workspace that is too small: U2GNN_E_ARG before anything is launched. */
+#define U2GNN_CLASS_ROWS_MAX 64      /* classes (64 x 64 columns x 4 row lanes x 4 B = the 64 KB of LDS a block takes) */
+#define U2GNN_CLASS_ROWS_CHUNK 256   /* rows per block of stage one */
+#define U2GNN_CLASS_ROWS_K(n_rows) \
+    (U2GNN_CLASS_ROWS_CHUNK / 4 + 2 + (((n_rows) + U2GNN_CLASS_ROWS_CHUNK - 1) / U2GNN_CLASS_ROWS_CHUNK + 15) / 16 + 4)
+int u2gnn_gather_rows_emb(const float *src, int64_t ld_src, int64_t src_rows, const int64_t *idx, int64_t idx_stride,
+                          float *dst, int64_t ld_dst, int64_t n_rows, int64_t n_rows_pad, int64_t d, int64_t d_pad,
+                          const int32_t *deg, const float *emb, int64_t ld_emb, int32_t n_classes, int32_t *err,
+                          void *stream);
+int64_t u2gnn_class_rows_grad_ws_floats(int64_t n_rows, int64_t d, int32_t n_classes);
+int u2gnn_class_rows_grad(const float *dX, int64_t ld, int64_t n_rows, int64_t d, const int64_t *idx,
+                          int64_t idx_stride, const int32_t *deg, int64_t src_rows, int32_t n_classes, float *demb,
+                          int64_t ld_demb, float *ws, int64_t ws_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
