@@ -236,9 +236,23 @@ __global__ void __launch_bounds__(256) sqnorm_final_kernel(const double *ws, int
     if (threadIdx.x == 0) out[0] = (float)(red[0] + red[1] + red[2] + red[3]);
 }
 
-// the element update of both Adam kernels; 16-byte loads of all four streams when the buffers allow
-// (one float per thread kept ~16 KB in flight per CU: C5's 326 MB sweep ran at 6 TB/s), the same
-// per-element arithmetic either way
+// One element of the update.  Both loops of adam_sweep call it, contraction is off inside it and the fused
+// multiply-adds are written out, so the float4 path and the scalar path round alike: left to the compiler, the two
+// loops fused different multiply-add pairs and exp_avg_sq differed in its last bit between an aligned and an
+// unaligned buffer.  The fused pairs are the ones the float4 loop had before (its results keep their bits).
+__device__ __forceinline__ void adam_update(float gi, float &mi, float &vi, float &pi, float coef, float b2, float w1,
+                                            float w2, float eps, float step_size, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float g = gi * coef;
+    mi = fmaf(w1, fmaf(gi, coef, -mi), mi);   // m + w1 (g - m)
+    vi = fmaf(g, w2 * g, vi * b2);            // v b2 + w2 g g
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi = fmaf(-step_size, mi / denom, pi);    // p - step_size m / denom
+}
+
+// the sweep of both Adam kernels; 16-byte loads of all four streams when the buffers allow (one float per thread
+// kept ~16 KB in flight per CU: C5's 326 MB sweep ran at 6 TB/s), the same per-element arithmetic either way
+// (adam_update)
 __device__ __forceinline__ void adam_sweep(float *param, const float *grad, float *m, float *v, int64_t n, float coef,
                                            float b2, float w1, float w2, float eps, float step_size, float bc2_sqrt) {
     const bool vec = ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
@@ -248,29 +262,20 @@ __device__ __forceinline__ void adam_sweep(float *param, const float *grad, floa
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += stride) {
         const float4 g4 = reinterpret_cast<const float4 *>(grad)[q], p4 = reinterpret_cast<const float4 *>(param)[q];
         const float4 m4 = reinterpret_cast<const float4 *>(m)[q], v4 = reinterpret_cast<const float4 *>(v)[q];
-        const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w};
-        const float mv[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-        float mo[4], vo[4], po[4];
+        const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
+        float po[4] = {p4.x, p4.y, p4.z, p4.w}, mo[4] = {m4.x, m4.y, m4.z, m4.w}, vo[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float g = gv[k] * coef;
-            mo[k] = mv[k] + w1 * (g - mv[k]);
-            vo[k] = vv[k] * b2 + w2 * g * g;
-            const float denom = sqrtf(vo[k]) / bc2_sqrt + eps;
-            po[k] = pv[k] - step_size * (mo[k] / denom);
-        }
+        for (int k = 0; k < 4; ++k) adam_update(gv[k], mo[k], vo[k], po[k], coef, b2, w1, w2, eps, step_size, bc2_sqrt);
         reinterpret_cast<float4 *>(m)[q] = make_float4(mo[0], mo[1], mo[2], mo[3]);
         reinterpret_cast<float4 *>(v)[q] = make_float4(vo[0], vo[1], vo[2], vo[3]);
         reinterpret_cast<float4 *>(param)[q] = make_float4(po[0], po[1], po[2], po[3]);
     }
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float g = grad[i] * coef;
-        const float mi = m[i] + w1 * (g - m[i]);
-        const float vi = v[i] * b2 + w2 * g * g;
+        float mi = m[i], vi = v[i], pi = param[i];
+        adam_update(grad[i], mi, vi, pi, coef, b2, w1, w2, eps, step_size, bc2_sqrt);
         m[i] = mi;
         v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        param[i] = param[i] - step_size * (mi / denom);
+        param[i] = pi;
     }
 }
 
